@@ -10,8 +10,17 @@ reported in "secondary".  With N > 1 GPUs every rank processes its own
 16 M-frame shard (weak scaling) and the per-frame flow hashes of each batch
 are all-gathered over RCCL, overlapped with the next batch's kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full ...
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs: it generates and places the
+C1500 batch, settles, warms up, times the K steps and prints the line.  With
+--dump-outputs DIR it then writes a fixed sample of the records the last
+timed step produced as DIR/*.npy.  Every other measurement and check (parity
+against the oracle, the box's HBM ceilings, compact records, the CPU
+baseline, the secondary configs, the batch ops, end to end, same-run PMC
+traffic) runs with --full.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement".
 """
@@ -361,6 +370,33 @@ def placed_gather(ctx, b, recs, kw, n_total, ws, rank, dev):
     rep["_freed_at"] = time.perf_counter()
     note_freed(rep.get("freed_bytes", 0), rep["_freed_at"])
     return gbs, rep
+
+
+DUMP_ROWS = 1 << 17       # records sampled by --dump-outputs (32 MB as float32)
+DUMP_SEED = 0xD0E5
+
+
+def dump_outputs(path, recs, n, gb=None):
+    """--dump-outputs: what the last timed step handed its caller, as .npy
+    files under `path`, for comparing two builds output for output.  The
+    record array is far above what is worth writing (1 GB at 16 M frames),
+    so a fixed, seeded sample of DUMP_ROWS frames is kept (all of them when
+    n is smaller): records.npy holds their records byte for byte (float32
+    [rows, record bytes], every value 0..255) and records_index.npy the
+    frames' indices (float64).  With an all-gather, gathered_hash.npy holds
+    the same slots of the gathered flow-hash array the step left (float32
+    [rows, 8], the bytes of each u64)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_ROWS),
+                                                          replace=False))
+    sel = torch.from_numpy(idx).to(recs.device)
+    rows = recs[sel].cpu().numpy()
+    np.save(os.path.join(path, "records.npy"), rows.astype(np.float32))
+    np.save(os.path.join(path, "records_index.npy"), idx.astype(np.float64))
+    if gb is not None:
+        h = gb.out.view(torch.uint8).view(-1, 8)[sel].cpu().numpy()
+        np.save(os.path.join(path, "gathered_hash.npy"), h.astype(np.float32))
 
 
 def run_config(cfg, n, ctx, dev, ws, rank, steps, warmup, gbs, check, settle=SETTLE_S,
@@ -1412,6 +1448,14 @@ def main():
                     help="frames per GPU (weak) or in total (strong)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --frames per GPU; strong: --frames split over the GPUs")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement and check beside the headline figure (parity, "
+                         "HBM ceilings, compact records, CPU baseline, secondary configs, batch "
+                         "ops, end to end, same-run PMC traffic); the --no-* options below "
+                         "drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the records the last "
+                         "step produced as DIR/*.npy (float32 / float64)")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-check", action="store_true")
@@ -1435,6 +1479,14 @@ def main():
                          "then comes from the committed summary)")
     args = ap.parse_args()
     launch_ranks(sys.argv[1:], args.gpus)
+    # the all-gathered hashes are checked whenever there is a gather: the
+    # multi-GPU line is not valid without (validate_line)
+    gather_check = not args.no_check
+    if not args.full:
+        # a plain run: the primary config's timed steps and nothing beside
+        for k in ("no_secondary", "no_cpu", "no_check", "no_rec32", "no_membench", "no_e2e",
+                  "no_live_pmc"):
+            setattr(args, k, True)
 
     import torch
     from pptk_amd.rx import RxContext
@@ -1483,6 +1535,12 @@ def main():
                       coll_stream=split[1] if split else None)
     gbs = prim.pop("_gbs")
     log(f"[rank {rank}] {primary_cfg}: {prim['mpkts']:.1f} Mpkts/s, kernel {prim['kernel_ms']:.3f} ms")
+    if args.dump_outputs and rank == 0:
+        # now, before anything else runs on the batch (the tx measurement
+        # rewrites its frames in place); the last timed step gathered into
+        # buffer (steps - 1) % 2
+        dump_outputs(args.dump_outputs, prim["_recs"], n,
+                     gbs[(args.steps - 1) & 1] if gbs and args.steps else None)
     gat_split = None
     if split:
         torch.cuda.synchronize(dev)
@@ -1513,7 +1571,7 @@ def main():
         if gat_split:
             gat["split"] = {k: gat_split[k] for k in ("ms", "algbw_gbs", "busbw_gbs")}
         gat["buffer_placement"] = prim.get("gather_placement")
-        if check:
+        if gather_check:
             gat["gathered_check"] = gathered_check(prim, gbs, n, dev)
         log(f"[rank {rank}] no gather: {nog['mpkts']:.1f} Mpkts/s; all-gather {gat}")
 

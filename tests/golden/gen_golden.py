@@ -44,6 +44,13 @@ and per-frame verdicts of the reference's ip_permitted / ipv6_permitted
 called once per subject frame in frame order (oracle/refgen.c
 ref_permit_batch), and refills by the reference's own timer function
 (ref_tokens_refill).
+
+iphash.npz holds what the reference's rate limiter and timer heap
+(iphash/iphash.c, timerlinkheap/timerlink.c, linked unmodified from
+oracle/_ref/obj into tests/c/iphash_scenario.c) return for the scenarios of
+tests/test_capi.py: per (family, prefix bits, initial tokens) the verdicts,
+the final token array and the number of timer firings, and the pops of one
+timer-heap exercise.
 """
 import os
 import sys
@@ -279,15 +286,35 @@ def gen_frag(ref):
     return out
 
 
+def gen_iphash():
+    import tempfile
+    import test_capi as t
+    with tempfile.TemporaryDirectory() as d:
+        L = t._build_iphash_harness(os.path.join(d, "ref.so"), True)
+        meta = [(f, b, i) for i in t.IPHASH_INITIALS for f, b in t.IPHASH_FAMILIES]
+        runs = [t.run_iphash_scenario(L, f, b, i) for f, b, i in meta]
+        n, pops = t.run_timer_heap(L)
+    return {"scn_meta": np.array(meta, np.uint32),
+            "scn_verdict": np.stack([r[0] for r in runs]),
+            "scn_tok": np.stack([r[1] for r in runs]),
+            "scn_fired": np.array([r[2] for r in runs], np.uint32),
+            "heap_n": np.int64(n), "heap_pops": pops}
+
+
 def main():
     build()
     ref = Reference()
     opts = make_opts(KEY, BITS4, BITS6, HASH_SIZE)
-    want = set(sys.argv[1:]) or set(SETS) | {"permit", "tx", "rewrite", "mss", "tcpopt", "frag"}
+    want = set(sys.argv[1:]) or set(SETS) | {"permit", "tx", "rewrite", "mss", "tcpopt", "frag",
+                                                   "iphash"}
     if "mss" in want:
         path = os.path.join(HERE, "mss.npz")
         np.savez_compressed(path, **gen_mss(ref))
         print(f"mss -> {os.path.getsize(path)} B")
+    if "iphash" in want:
+        path = os.path.join(HERE, "iphash.npz")
+        np.savez_compressed(path, **gen_iphash())
+        print(f"iphash -> {os.path.getsize(path)} B")
     if "tcpopt" in want:
         path = os.path.join(HERE, "tcpopt.npz")
         np.savez_compressed(path, **gen_tcpopt(ref))

@@ -71,6 +71,32 @@ def test_line_fits_the_stored_tail_and_carries_every_config():
         assert back["cpu_baseline"]["cores"] == _full()["cpu_baseline"]["cores"]
 
 
+def test_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """--dump-outputs: the same seeded sample of the record array on every
+    call (so two builds compare output for output), byte for byte as
+    float32, the frames' indices beside it, within 64 MB; a batch smaller
+    than the sample is written whole, in order."""
+    import numpy as np
+    import torch
+    n = bench.DUMP_ROWS + 1000
+    recs = torch.from_numpy(np.random.default_rng(7).integers(0, 256, (n, 64), dtype=np.uint8))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), recs, n)
+    assert sorted(os.listdir(tmp_path / "a")) == ["records.npy", "records_index.npy"]
+    rows, idx = (np.load(tmp_path / "a" / f) for f in ("records.npy", "records_index.npy"))
+    assert rows.dtype == np.float32 and rows.shape == (bench.DUMP_ROWS, 64)
+    assert idx.dtype == np.float64 and idx.shape == (bench.DUMP_ROWS,)
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(rows, recs.numpy()[idx.astype(np.int64)].astype(np.float32))
+    for f in ("records.npy", "records_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "a" / f))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    bench.dump_outputs(str(tmp_path / "small"), recs[:100, :32].contiguous(), 100)
+    assert np.array_equal(np.load(tmp_path / "small" / "records_index.npy"), np.arange(100.0))
+    assert np.array_equal(np.load(tmp_path / "small" / "records.npy"),
+                          recs[:100, :32].numpy().astype(np.float32))
+
+
 def test_compact_multigpu_line_passes_validation():
     line = bench.compact_line(_full(8))
     assert bench.validate_line(line) == []

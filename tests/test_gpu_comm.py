@@ -156,7 +156,8 @@ def test_bench_one_rank_rccl_path(tmp_path, frames, scaling):
     from conftest import ROOT
     env = dict(os.environ, PPTK_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29600 + os.getpid() % 300))
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", str(frames),
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full",
+                          "--frames", str(frames),
                           "--scaling", scaling, "--steps", "3", "--warmup", "1", "--no-secondary",
                           "--no-cpu", "--no-rec32", "--no-membench", "--settle", "0.1"],
                          capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
