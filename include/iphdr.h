@@ -177,6 +177,30 @@ static inline uint16_t udp_cksum(const void *l4) { return hdr_get16n(PPTK_AT(l4,
  * stored big-endian. */
 #define PPTK_W(p, k) ((unsigned char *)(p) + (k))
 static inline void ip_set_ttl(void *pkt, uint8_t ttl) { *PPTK_W(pkt, 8) = ttl; }
+/* fragmentation fields: iphdr.h:949-953 (total length), 1099-1103 (id),
+ * 1130-1144 (offset), 1029-1038, 1046-1055, 1076-1091 (the three flag bits),
+ * 1283-1286 (payload).  ip_set_frag_off abort()s on an offset that is not a
+ * multiple of 8, as the reference does; every flag setter leaves the other
+ * bits of byte 6 as they were. */
+static inline void ip_set_total_len(void *pkt, uint16_t total_len) { hdr_set16n(PPTK_W(pkt, 2), total_len); }
+static inline void ip_set_id(void *pkt, uint16_t id) { hdr_set16n(PPTK_W(pkt, 4), id); }
+static inline void ip_set_frag_off(void *pkt, uint16_t frag_off)
+{
+  if (frag_off % 8 != 0)
+    abort();
+  frag_off /= 8;
+  *PPTK_W(pkt, 6) = (unsigned char)((*PPTK_AT(pkt, 6) & ~0x1f) | ((frag_off >> 8) & 0x1f));
+  *PPTK_W(pkt, 7) = (unsigned char)(frag_off & 0xff);
+}
+static inline void pptk_ip_set_flag(void *pkt, unsigned mask, int bit)
+{
+  *PPTK_W(pkt, 6) = (unsigned char)((*PPTK_AT(pkt, 6) & ~mask) | (bit ? mask : 0u));
+}
+static inline void ip_set_more_frags(void *pkt, int bit) { pptk_ip_set_flag(pkt, 0x20, bit); }
+static inline void ip_set_dont_frag(void *pkt, int bit) { pptk_ip_set_flag(pkt, 0x40, bit); }
+static inline int ip_rsvd_bit(const void *pkt) { return *PPTK_AT(pkt, 6) & 0x80; }
+static inline void ip_set_rsvd_bit(void *pkt, int bit) { pptk_ip_set_flag(pkt, 0x80, bit); }
+static inline void *ip_payload(void *pkt) { return (unsigned char *)pkt + ip_hdr_len(pkt); }
 static inline void ip_set_hdr_cksum(void *pkt, uint16_t c) { hdr_set16n(PPTK_W(pkt, 10), c); }
 static inline void ip_set_src(void *pkt, uint32_t src) { hdr_set32n(PPTK_W(pkt, 12), src); }
 static inline void ip_set_dst(void *pkt, uint32_t dst) { hdr_set32n(PPTK_W(pkt, 16), dst); }

@@ -430,6 +430,86 @@ int pptk_tcp_mss_clamp_device(struct pptk_rx_ctx *ctx, uint8_t *d_frames, const 
                               uint64_t n, uint16_t mss, uint32_t flags, uint8_t *d_status,
                               void *stream);
 
+/* IPv4 fragmentation to an egress MTU (forwarder / tunnel ingress), the
+ * batch form of the reference's fragment4() (ipfrag/ipfrag.c:11-123) with
+ * the plan "as few fragments as possible".  `mtu` (68..65535) counts the IP
+ * packet without L2.  Per frame, parsed exactly as pptk_rx_batch_device
+ * parses: a frame whose record would be PARSED, not MALFORMED and not IPV6
+ * is a subject (status PPTK_FRAG_ST_IPV4); everything else gets status 0 and
+ * count 0.  With l2 = l3_off, ihl = ip_hdr_len, tl = ip_total_len and
+ * datamax = tl - ihl (Ethernet padding past l2 + tl is ignored, as calling
+ * fragment4 with sz = 14 + tl ignores it):
+ *   tl <= mtu    PPTK_FRAG_ST_FITS, count 0: the caller sends the original.
+ *   otherwise    PPTK_FRAG_ST_DF if ip_dont_frag, PPTK_FRAG_ST_ISFRAG if
+ *                ip_more_frags or ip_frag_off != 0, PPTK_FRAG_ST_BADCKSUM if
+ *                ip_hdr_cksum_calc(ip, ihl) != 0 -- the conditions under
+ *                which fragment4 abort()s (:42-61); with any of them count
+ *                is 0 and nothing is emitted (DF: answer with ICMP).
+ *   else         PPTK_FRAG_ST_DONE: per = (mtu - ihl) & ~7, count =
+ *                ceil(datamax / per); fragment j carries datastart = j * per
+ *                and datalen = min(per, datamax - datastart).
+ * A fragment is what fragment4 writes (:106-121): the frame's first l2 + ihl
+ * bytes (every IP option goes into every fragment, as in the reference),
+ * ip_set_frag_off(datastart), ip_set_more_frags(datastart + datalen <
+ * datamax) -- the reserved and DF bits stay --, ip_set_total_len(ihl +
+ * datalen), ip_set_hdr_cksum_calc(ip, ihl), then datalen payload bytes from
+ * frame + l2 + ihl + datastart; its length is l2 + ihl + datalen.
+ *
+ * Output: first[i] = the exclusive prefix sum of the counts; the fragments
+ * of frame i fill slots first[i] .. first[i] + count[i] - 1 in ascending
+ * offset, slot s at d_out + s * out_stride: bytes [0, len) the fragment,
+ * bytes [len, round_up(len, 16)) zero, the rest of the slot untouched.  A
+ * DONE frame with first[i] + count[i] > out_cap also gets
+ * PPTK_FRAG_ST_NOROOM and none of its slots is written (so every later DONE
+ * frame has it too; earlier frames are complete).  d_out_len[s] / d_out_src[s]
+ * (nullable) receive the length and the source frame index of every written
+ * slot; d_first / d_count / d_status (nullable) the per-frame words (d_first
+ * holds the low 32 bits); d_totals[0] the slots the batch needs, d_totals[1]
+ * the slots written.  The slots can go straight back into
+ * pptk_rx_batch_device (stride = out_stride, d_len = d_out_len) or
+ * pptk_tx_cksum_device.
+ *
+ * d_out must be 16-byte aligned, out_stride a multiple of 16 and >=
+ * round_up(18 + mtu, 16), n <= 2^24 and out_cap < 2^32 (-EINVAL otherwise).  Layout arguments
+ * and the frame read bounds are those of pptk_tx_cksum_device /
+ * pptk_rx_dev_batch (no frame shorter than 14 bytes is read at all).  n = 0
+ * writes d_totals = {0, 0}.  d_scratch: pptk_ip_fragment_scratch_bytes(n)
+ * bytes, 16-byte aligned, no initialisation needed, in use until the stream
+ * reaches the end of the call.  Asynchronous on `stream`.
+ *
+ * Out of scope: re-fragmenting fragments (ISFRAG), IPv6, the "copied" flag
+ * of IP options (the reference copies all of them), and a host
+ * ldp_packet[] in -> host out batch path (pptk_ip_fragment_host is per
+ * packet). */
+#define PPTK_FRAG_ST_IPV4 0x01u      /* a subject: parsed IPv4                */
+#define PPTK_FRAG_ST_FITS 0x02u      /* tl <= mtu: send the original          */
+#define PPTK_FRAG_ST_DONE 0x04u      /* fragmented into count slots           */
+#define PPTK_FRAG_ST_DF 0x08u        /* too big and DF set                    */
+#define PPTK_FRAG_ST_ISFRAG 0x10u    /* too big and already a fragment        */
+#define PPTK_FRAG_ST_BADCKSUM 0x20u  /* too big and a bad header checksum     */
+#define PPTK_FRAG_ST_NOROOM 0x40u    /* DONE but past out_cap: not written    */
+size_t pptk_ip_fragment_scratch_bytes(uint64_t n);
+int pptk_ip_fragment_device(struct pptk_rx_ctx *ctx, const uint8_t *d_frames,
+                            const uint64_t *d_off, const uint16_t *d_len, uint64_t stride,
+                            uint32_t fixed_len, uint64_t n, uint32_t mtu, uint8_t *d_out,
+                            uint64_t out_stride, uint64_t out_cap, uint16_t *d_out_len,
+                            uint32_t *d_out_src, uint32_t *d_first, uint32_t *d_count,
+                            uint8_t *d_status, uint64_t *d_totals, void *d_scratch,
+                            void *stream);
+
+/* The per-packet host form, and the CPU statement of the contract above
+ * (plain C over iphdr.h / ipcksum.h, pptk_amd/csrc/host/ipfrag.c): the same
+ * rules and the same slot layout for one frame.  Returns the fragment count
+ * (0 unless *status has DONE) or -EINVAL (a null frame with len > 0, a null
+ * out, out_len or status, an mtu outside 68..65535, an out_stride that is
+ * not a multiple of 16 or is below round_up(18 + mtu, 16); *status is then
+ * not written).  With count > out_cap the status gets NOROOM,
+ * nothing is written and the count is still returned.  `out` needs no
+ * alignment. */
+int pptk_ip_fragment_host(const void *frame, uint32_t len, uint32_t mtu, uint8_t *out,
+                          uint64_t out_stride, uint32_t out_cap, uint16_t *out_len,
+                          uint8_t *status);
+
 /* Tuning: force kernel variant `variant` (0 .. pptk_rx_variant_count()-1)
  * and/or memory-policy flags for every later batch of this context; -1
  * restores the automatic choice (variant by frame length and alignment).

@@ -1,0 +1,456 @@
+// tx_frag.hip -- pptk_ip_fragment_device: batched IPv4 fragmentation to an
+// egress MTU (include/pptk_rx.h; reference ipfrag/ipfrag.c:11-123,
+// fragment4).  Unlike the receive kernels the output size depends on the
+// data, so the call runs in four launches:
+//   plan   one lane per frame: the receive transform's structural IPv4
+//          parse, the header checksum, status and fragment count; a block
+//          scan leaves each frame's prefix inside its 256-frame tile
+//   scan   one block: exclusive prefix of the tile sums, totals[0]
+//   apply  one lane per frame: first[i], NOROOM, the caller's per-frame
+//          arrays, totals[1]
+//   emit   a team of 16 lanes per 16 frames walks the DONE frames among
+//          them and copies each one's fragments, 16-byte chunk by chunk: a
+//          re-aligning copy, the source at any byte offset, the destination
+//          slot 16-byte aligned
+// The scan is the classic three-launch one: nothing waits on another
+// workgroup.
+#include <errno.h>
+
+#include "rx_internal.h"
+
+namespace pptk {
+namespace {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#define LDS_AS __attribute__((address_space(3)))
+
+constexpr int kTile = 256;                  // frames per plan / apply block = scan tile
+constexpr int kScanThreads = 1024;
+constexpr uint64_t kMaxFrames = 1ull << 24; // 65536 tiles: one scan block
+constexpr int kTeam = 16;                   // lanes per source frame in the emit kernel
+constexpr int kUnroll = 4;                  // team rounds whose loads are in flight together
+
+struct FragArgs {
+  const uint8_t *frames;
+  const uint64_t *off;   // nullable -> fixed stride
+  const uint16_t *len;   // nullable -> fixed_len
+  uint64_t stride;
+  uint64_t n;
+  uint32_t fixed_len;
+  uint32_t mtu;
+  uint8_t *out;
+  uint64_t out_stride;
+  uint64_t out_cap;
+  uint16_t *out_len;     // nullable
+  uint32_t *out_src;     // nullable
+  uint32_t *first;       // nullable
+  uint32_t *count;       // nullable
+  uint8_t *status;       // nullable
+  uint64_t *totals;
+  // scratch
+  uint64_t *s_info;      // DONE frames: S0 | tl << 16 | ihl << 32 | l2 << 40 | kept flag bits << 48
+  uint64_t *s_tile;      // tile sums, then their exclusive prefix
+  uint32_t *s_cnt;
+  uint32_t *s_first;     // prefix inside the tile, then the global one
+  uint8_t *s_st;
+};
+
+constexpr uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
+
+struct ScratchLayout {
+  uint64_t info, tile, cnt, first, st, total;
+};
+ScratchLayout scratch_layout(uint64_t n) {
+  ScratchLayout l;
+  const uint64_t ntiles = (n + kTile - 1) / kTile;
+  l.info = 0;
+  l.tile = l.info + up16(n * 8);
+  l.cnt = l.tile + up16(ntiles * 8);
+  l.first = l.cnt + up16(n * 4);
+  l.st = l.first + up16(n * 4);
+  l.total = l.st + up16(n);
+  return l;
+}
+
+__device__ __forceinline__ uint32_t bswap16(uint32_t x) {
+  return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu);
+}
+
+// end-around-carry fold, as the reference's loop (iphdr/ipcksum.h:17-25)
+__device__ __forceinline__ uint32_t fold16(uint32_t s) {
+  s = (s & 0xffffu) + (s >> 16);
+  s = (s & 0xffffu) + (s >> 16);
+  return s;
+}
+
+__device__ __forceinline__ uint32_t halves(uint32_t w) { return (w & 0xffffu) + (w >> 16); }
+
+__device__ __forceinline__ uint32_t ld_u8(uintptr_t A) { return *(const uint8_t *)A; }
+
+// Four bytes at any byte address as a little-endian dword, from the one or
+// two aligned dwords that hold them (both inside the frame when the four
+// bytes are).
+__device__ __forceinline__ uint32_t ld_le32(uintptr_t A) {
+  const uint32_t *w = (const uint32_t *)(A & ~(uintptr_t)3);
+  const uint32_t r = (uint32_t)(A & 3);
+  const uint32_t lo = w[0], hi = w[r ? 1 : 0];
+  return __builtin_amdgcn_alignbyte(hi, lo, r);
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t lo = __shfl_up((uint32_t)v, d, 64);
+    const uint32_t hi = __shfl_up((uint32_t)(v >> 32), d, 64);
+    if (lane >= d) v += (uint64_t)lo | ((uint64_t)hi << 32);
+  }
+  return v;
+}
+
+// ---- plan ------------------------------------------------------------------
+// The subject test is the IPv4 branch of the receive transform's parse
+// (rx_kernel.hip parse_frame): one optional 802.1Q tag, ethertype 0x0800,
+// version 4, 20 <= ihl <= tl, l2 + tl <= len.  A frame shorter than 14 bytes
+// is not read at all; every other read lies inside the frame.
+__global__ __launch_bounds__(kTile) void frag_plan_kernel(FragArgs a) {
+  __shared__ uint32_t wsum[kTile / 64];
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  uint32_t st = 0, cnt = 0;
+  if (i < a.n) {
+    const uint64_t base = a.off ? a.off[i] : i * a.stride;
+    const uint32_t len = a.len ? a.len[i] : a.fixed_len;
+    const uintptr_t F = (uintptr_t)a.frames + base;
+    if (len >= 14 && len <= 65535) {
+      uint32_t et = (ld_u8(F + 12) << 8) | ld_u8(F + 13), l2 = 14;
+      if (et == 0x8100 && len >= 18) {
+        et = (ld_u8(F + 16) << 8) | ld_u8(F + 17);
+        l2 = 18;
+      }
+      if (et == 0x0800 && len >= l2 + 20) {
+        const uintptr_t ip = F + l2;
+        const uint32_t w0 = ld_le32(ip), w1 = ld_le32(ip + 4), w2 = ld_le32(ip + 8);
+        const uint32_t b0 = w0 & 0xffu, ihl = (b0 & 15u) * 4u;
+        const uint32_t tl = bswap16(w0 >> 16);
+        if ((b0 >> 4) == 4 && ihl >= 20 && tl >= ihl && l2 + tl <= len) {
+          st = PPTK_FRAG_ST_IPV4;
+          if (tl <= a.mtu) {
+            st |= PPTK_FRAG_ST_FITS;
+          } else {
+            // the header's one's-complement sum over little-endian halves
+            // (byte order does not matter to the fold); s0 leaves out the
+            // three fields every fragment rewrites: total length, flags +
+            // offset, checksum
+            uint32_t s0 = (w0 & 0xffffu) + (w1 & 0xffffu) + (w2 & 0xffffu) +
+                          halves(ld_le32(ip + 12)) + halves(ld_le32(ip + 16));
+            for (uint32_t k = 20; k < ihl; k += 4) s0 += halves(ld_le32(ip + k));
+            const uint32_t all = s0 + (w0 >> 16) + (w1 >> 16) + (w2 >> 16);
+            const uint32_t fw = bswap16(w1 >> 16);
+            if (fw & 0x4000u) st |= PPTK_FRAG_ST_DF;
+            if (fw & 0x3fffu) st |= PPTK_FRAG_ST_ISFRAG;
+            if (fold16(all) != 0xffffu) st |= PPTK_FRAG_ST_BADCKSUM;
+            if (st == PPTK_FRAG_ST_IPV4) {
+              st |= PPTK_FRAG_ST_DONE;
+              const uint32_t per = (a.mtu - ihl) & ~7u;
+              cnt = (tl - ihl + per - 1) / per;
+              // s0 holds the version byte, so its fold is 1..0xffff
+              a.s_info[i] = (uint64_t)bswap16(fold16(s0)) | ((uint64_t)tl << 16) |
+                            ((uint64_t)ihl << 32) | ((uint64_t)l2 << 40) |
+                            ((uint64_t)(fw & 0xc000u) << 48);
+            }
+          }
+        }
+      }
+    }
+    a.s_cnt[i] = cnt;
+    a.s_st[i] = (uint8_t)st;
+  }
+  // exclusive prefix inside the tile (at most 256 * 8190 slots: 32 bits)
+  const uint32_t inc = wave_incl_scan(cnt);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) wsum[wave] = inc;
+  __syncthreads();
+  uint32_t wbase = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < kTile / 64; ++w) {
+    if (w < wave) wbase += wsum[w];
+    total += wsum[w];
+  }
+  if (i < a.n) a.s_first[i] = wbase + inc - cnt;
+  if (threadIdx.x == 0) a.s_tile[blockIdx.x] = total;
+}
+
+// ---- scan ------------------------------------------------------------------
+__global__ __launch_bounds__(kScanThreads) void frag_scan_kernel(FragArgs a, uint32_t ntiles) {
+  __shared__ uint64_t wsum[kScanThreads / 64];
+  const uint32_t per = (ntiles + kScanThreads - 1) / kScanThreads;
+  const uint32_t lo = min(threadIdx.x * per, ntiles), hi = min(lo + per, ntiles);
+  uint64_t s = 0;
+  for (uint32_t t = lo; t < hi; ++t) s += a.s_tile[t];
+  const uint64_t inc = wave_incl_scan64(s);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) wsum[wave] = inc;
+  __syncthreads();
+  uint64_t run = inc - s, total = 0;
+#pragma unroll
+  for (int w = 0; w < kScanThreads / 64; ++w) {
+    if (w < wave) run += wsum[w];
+    total += wsum[w];
+  }
+  for (uint32_t t = lo; t < hi; ++t) {
+    const uint64_t v = a.s_tile[t];
+    a.s_tile[t] = run;
+    run += v;
+  }
+  if (threadIdx.x == 0) {
+    a.totals[0] = total;
+    // otherwise the one frame that straddles out_cap writes it (apply)
+    if (total <= a.out_cap) a.totals[1] = total;
+  }
+}
+
+// ---- apply -----------------------------------------------------------------
+__global__ __launch_bounds__(kTile) void frag_apply_kernel(FragArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  if (i >= a.n) return;
+  const uint64_t first = a.s_tile[blockIdx.x] + a.s_first[i];
+  const uint32_t cnt = a.s_cnt[i];
+  uint32_t st = a.s_st[i];
+  if (cnt && first + cnt > a.out_cap) {
+    st |= PPTK_FRAG_ST_NOROOM;
+    a.s_st[i] = (uint8_t)st;
+    // the slot intervals of the DONE frames are disjoint and ascending:
+    // exactly one of them holds out_cap when the batch does not fit
+    if (first <= a.out_cap) a.totals[1] = first;
+  }
+  a.s_first[i] = (uint32_t)first;
+  if (a.first) a.first[i] = (uint32_t)first;
+  if (a.count) a.count[i] = cnt;
+  if (a.status) a.status[i] = (uint8_t)st;
+}
+
+// ---- emit ------------------------------------------------------------------
+// 16 bytes from any byte address A, of which only those below `lim` (> A)
+// are meaningful: the aligned chunk holding A and the aligned chunk holding
+// the last needed byte (the same or the next one), funnelled to A's
+// alignment.  Nothing outside the aligned chunks of [A, lim) is read.  The
+// loads and the funnel are separate so that a lane can have the chunks of
+// several rounds in flight before it shifts the first.
+struct Raw16 {
+  u32x4 lo, hi;
+};
+
+__device__ __forceinline__ Raw16 load16_raw(uintptr_t A, uintptr_t lim) {
+  const uintptr_t end = A + 16 < lim ? A + 16 : lim;
+  Raw16 r;
+  r.lo = __builtin_nontemporal_load((const u32x4 *)(A & ~(uintptr_t)15));
+  r.hi = __builtin_nontemporal_load((const u32x4 *)((end - 1) & ~(uintptr_t)15));
+  return r;
+}
+
+__device__ __forceinline__ u32x4 funnel16(const Raw16 &c, uintptr_t A) {
+  const uint32_t sh = (uint32_t)(A & 15), r = sh & 3u;
+  // dword select in two steps (by 2, by 1), then the byte funnel
+  const bool s2 = sh & 8u, s1 = sh & 4u;
+  const uint32_t f0 = s2 ? c.lo.z : c.lo.x, f1 = s2 ? c.lo.w : c.lo.y, f2 = s2 ? c.hi.x : c.lo.z;
+  const uint32_t f3 = s2 ? c.hi.y : c.lo.w, f4 = s2 ? c.hi.z : c.hi.x, f5 = s2 ? c.hi.w : c.hi.y;
+  const uint32_t e0 = s1 ? f1 : f0, e1 = s1 ? f2 : f1, e2 = s1 ? f3 : f2, e3 = s1 ? f4 : f3;
+  const uint32_t e4 = s1 ? f5 : f4;
+  u32x4 o;
+  o.x = __builtin_amdgcn_alignbyte(e1, e0, r);
+  o.y = __builtin_amdgcn_alignbyte(e2, e1, r);
+  o.z = __builtin_amdgcn_alignbyte(e3, e2, r);
+  o.w = __builtin_amdgcn_alignbyte(e4, e3, r);
+  return o;
+}
+
+__device__ __forceinline__ u32x4 load16(uintptr_t A, uintptr_t lim) {
+  return funnel16(load16_raw(A, lim), A);
+}
+
+// mask of the first nb bytes of a dword (nb may be <= 0 or >= 4)
+__device__ __forceinline__ uint32_t low_bytes(int nb) {
+  return nb <= 0 ? 0u : (nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u);
+}
+
+// the big-endian 16-bit field at slot offset pos (even) := val, if it lies in
+// the chunk at slot offset o
+__device__ __forceinline__ void put16(u32x4 &v, uint32_t o, uint32_t pos, uint32_t val) {
+  const uint32_t rel = pos - o;
+  if (rel >= 16) return;
+  const uint32_t sh = (rel & 3u) * 8u, le = bswap16(val) << sh, keep = ~(0xffffu << sh);
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+    if ((rel >> 2) == (uint32_t)d) v[d] = (v[d] & keep) | le;
+}
+
+__device__ __forceinline__ void emit_frame(const FragArgs &a, uint64_t i, uint32_t t,
+                                           LDS_AS u32x4 *hds) {
+  const uint64_t base = a.off ? a.off[i] : i * a.stride;
+  const uint64_t info = a.s_info[i];
+  const uint32_t first = a.s_first[i], count = a.s_cnt[i];
+  const uint32_t s0 = (uint32_t)info & 0xffffu, tl = (uint32_t)(info >> 16) & 0xffffu;
+  const uint32_t ihl = (uint32_t)(info >> 32) & 0xffu, l2 = (uint32_t)(info >> 40) & 0xffu;
+  const uint32_t fkeep = (uint32_t)(info >> 48);   // the reserved bit (DF is clear)
+  const uint32_t H = l2 + ihl, datamax = tl - ihl, per = (a.mtu - ihl) & ~7u;
+  const uintptr_t F = (uintptr_t)a.frames + base;
+
+  // lengths and source indices of the frame's slots, a run of `count`
+  for (uint32_t j = t; j < count; j += kTeam) {
+    const uint32_t left = datamax - j * per;
+    if (a.out_len) a.out_len[first + j] = (uint16_t)(H + (left < per ? left : per));
+    if (a.out_src) a.out_src[first + j] = (uint32_t)i;
+  }
+
+  // the header chunks, once per frame, parked in the team's LDS slot: chunk c
+  // = slot bytes [16c, 16c + 16) as far as they are header (at most five:
+  // H <= 78).  The team's lanes are in one wave, whose LDS accesses keep
+  // their order.
+  __builtin_amdgcn_wave_barrier();
+  if (16 * t < H) hds[t] = load16(F + 16 * t, F + H);
+  __builtin_amdgcn_wave_barrier();
+
+  // The frame's chunks as one index space across its fragments: c0 chunks for
+  // every fragment but the last.  The team takes kTeam * kUnroll of them per
+  // pass, whatever fragment they fall into, and issues all their loads before
+  // the first chunk is shifted and stored.
+  const uint32_t c0 = (H + per + 15) >> 4, last = count - 1;
+  const uint32_t nchunks = last * c0 + ((H + datamax - last * per + 15) >> 4);
+  for (uint32_t q0 = t; q0 < nchunks; q0 += kTeam * kUnroll) {
+    Raw16 raw[kUnroll];
+    uint32_t fj[kUnroll], fo[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const uint32_t q = q0 + kTeam * u;
+      if (q < nchunks) {
+        const uint32_t j = min(q / c0, last), o = (q - j * c0) * 16u;
+        const uint32_t ds = j * per, left = datamax - ds, flen = H + (left < per ? left : per);
+        fj[u] = j;
+        fo[u] = o;
+        // slot byte o >= H is frame byte o + ds
+        if (o + 16 > H) raw[u] = load16_raw(F + ds + o, F + ds + flen);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      if (q0 + kTeam * u < nchunks) {
+        const uint32_t j = fj[u], o = fo[u];
+        const uint32_t ds = j * per, left = datamax - ds, dl = left < per ? left : per;
+        const uint32_t flen = H + dl;
+        u32x4 v = {0, 0, 0, 0};
+        if (o + 16 > H) v = funnel16(raw[u], F + ds + o);
+        if (o < H) {   // a header chunk, the last one mixed with payload
+          const uint32_t ntl = ihl + dl;                                   // ip_set_total_len
+          const uint32_t nfw = fkeep | (ds + dl < datamax ? 0x2000u : 0u) | (ds >> 3);
+          const uint32_t ck = ~fold16(s0 + ntl + nfw) & 0xffffu;            // ip_set_hdr_cksum_calc
+          const u32x4 hd = hds[o >> 4];
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            const uint32_t m = low_bytes((int)H - (int)o - 4 * d);
+            v[d] = (hd[d] & m) | (v[d] & ~m);
+          }
+          put16(v, o, l2 + 2, ntl);
+          put16(v, o, l2 + 6, nfw);
+          put16(v, o, l2 + 10, ck);
+        }
+        if (flen - o < 16) {   // zeros up to the next 16-byte boundary
+#pragma unroll
+          for (int d = 0; d < 4; ++d) v[d] &= low_bytes((int)(flen - o) - 4 * d);
+        }
+        *(u32x4 *)(a.out + (uint64_t)(first + j) * a.out_stride + o) = v;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void frag_emit_kernel(FragArgs a) {
+  __shared__ u32x4 hdr_lds[256 / kTeam][5];
+  LDS_AS u32x4 *hds = (LDS_AS u32x4 *)&hdr_lds[threadIdx.x / kTeam][0];
+  const uint32_t t = threadIdx.x & (kTeam - 1);
+  const uint64_t team = ((uint64_t)blockIdx.x * 256u + threadIdx.x) / kTeam;
+  const uint64_t step = (uint64_t)gridDim.x * 256u;
+  for (uint64_t g = team * kTeam; g < a.n; g += step) {
+    // each lane looks at one of the team's 16 frames; the team then walks
+    // those that are to be written
+    const uint32_t st = g + t < a.n ? a.s_st[g + t] : 0u;
+    const bool go = (st & (PPTK_FRAG_ST_DONE | PPTK_FRAG_ST_NOROOM)) == PPTK_FRAG_ST_DONE;
+    uint32_t mask = (uint32_t)(__ballot(go) >> (threadIdx.x & 48u)) & 0xffffu;
+    while (mask) {
+      const uint32_t k = (uint32_t)__builtin_ctz(mask);
+      mask &= mask - 1;
+      emit_frame(a, g + k, t, hds);
+    }
+  }
+}
+
+int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
+
+}  // namespace
+}  // namespace pptk
+
+using namespace pptk;
+
+extern "C" size_t pptk_ip_fragment_scratch_bytes(uint64_t n) {
+  return (size_t)scratch_layout(n).total + 64;
+}
+
+extern "C" int pptk_ip_fragment_device(struct pptk_rx_ctx *c, const uint8_t *d_frames,
+                                       const uint64_t *d_off, const uint16_t *d_len,
+                                       uint64_t stride, uint32_t fixed_len, uint64_t n,
+                                       uint32_t mtu, uint8_t *d_out, uint64_t out_stride,
+                                       uint64_t out_cap, uint16_t *d_out_len, uint32_t *d_out_src,
+                                       uint32_t *d_first, uint32_t *d_count, uint8_t *d_status,
+                                       uint64_t *d_totals, void *d_scratch, void *stream) {
+  if (!c || !d_totals || n > kMaxFrames || mtu < 68 || mtu > 65535) return -EINVAL;
+  if (((uintptr_t)d_out & 15u) || (out_stride & 15u) || out_stride < up16(18u + (uint64_t)mtu) ||
+      out_cap > 0xffffffffull || (!d_out && out_cap))
+    return -EINVAL;
+  if (n && (!d_frames || !d_scratch || ((uintptr_t)d_scratch & 15u) ||
+            (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535)))
+    return -EINVAL;
+  DeviceScope dg(ctx_device(c));
+  if (!dg.ok) return -EIO;
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) return hip_rc(hipMemsetAsync(d_totals, 0, 2 * sizeof(uint64_t), s));
+
+  const ScratchLayout l = scratch_layout(n);
+  uint8_t *sc = (uint8_t *)d_scratch;
+  FragArgs a;
+  a.frames = d_frames;
+  a.off = d_off;
+  a.len = d_len;
+  a.stride = stride;
+  a.n = n;
+  a.fixed_len = fixed_len;
+  a.mtu = mtu;
+  a.out = d_out;
+  a.out_stride = out_stride;
+  a.out_cap = out_cap;
+  a.out_len = d_out_len;
+  a.out_src = d_out_src;
+  a.first = d_first;
+  a.count = d_count;
+  a.status = d_status;
+  a.totals = d_totals;
+  a.s_info = (uint64_t *)(sc + l.info);
+  a.s_tile = (uint64_t *)(sc + l.tile);
+  a.s_cnt = (uint32_t *)(sc + l.cnt);
+  a.s_first = (uint32_t *)(sc + l.first);
+  a.s_st = sc + l.st;
+  const uint32_t ntiles = (uint32_t)((n + kTile - 1) / kTile);
+  hipLaunchKernelGGL(frag_plan_kernel, dim3(ntiles), dim3(kTile), 0, s, a);
+  hipLaunchKernelGGL(frag_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, a, ntiles);
+  hipLaunchKernelGGL(frag_apply_kernel, dim3(ntiles), dim3(kTile), 0, s, a);
+  hipLaunchKernelGGL(frag_emit_kernel, dim3(ntiles), dim3(256), 0, s, a);
+  return hip_rc(hipGetLastError());
+}

@@ -33,6 +33,9 @@ RW_ST_IP, RW_ST_L4, RW_ST_TTL_ZERO, RW_ST_EXPIRED, RW_ST_ICMP = 0x1, 0x2, 0x4, 0
 RW_ICMP_ID = 0x20
 MSS_SYN_ONLY = 0x1
 MSS_ST_TCP, MSS_ST_FOUND, MSS_ST_CLAMPED, MSS_ST_BADOPT = 0x1, 0x2, 0x4, 0x8
+# PPTK_FRAG_ST_*: per-frame status of pptk_ip_fragment_device / _host
+(FRAG_ST_IPV4, FRAG_ST_FITS, FRAG_ST_DONE, FRAG_ST_DF, FRAG_ST_ISFRAG, FRAG_ST_BADCKSUM,
+ FRAG_ST_NOROOM) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
 
 REC32_DTYPE = np.dtype([
     ("flow_hash", "<u8"),

@@ -178,7 +178,8 @@ EXPORTS = ("pptk_rx_opts_default", "pptk_rx_ctx_create", "pptk_rx_ctx_destroy",
            "pptk_rx_permit_scratch_bytes", "pptk_rx_permit_device", "pptk_rx_permit_keys_device",
            "pptk_rx_permit_status", "pptk_rx_tokens_refill_device", "pptk_tx_cksum_device", "pptk_tx_set_side_buffer",
            "pptk_tx_rewrite_device",
-           "pptk_tcp_mss_clamp_device", "pptk_rx_autotune", "pptk_rx_place_records",
+           "pptk_tcp_mss_clamp_device", "pptk_ip_fragment_scratch_bytes",
+           "pptk_ip_fragment_device", "pptk_ip_fragment_host", "pptk_rx_autotune", "pptk_rx_place_records",
            "pptk_rx_place_buffers", "pptk_rx_ring_alloc", "pptk_rx_ring_free",
            "pptk_rx_gather_alloc", "pptk_rx_gather_free",
            # multi-GPU (RCCL)
@@ -278,6 +279,17 @@ def lib(path=None):
                                                     ctypes.c_uint32, ctypes.c_uint64,
                                                     ctypes.c_uint16, ctypes.c_uint32, vp, vp]
             L.pptk_tcp_mss_clamp_device.restype = ctypes.c_int
+        if hasattr(L, "pptk_ip_fragment_device"):      # absent from older A/B builds
+            L.pptk_ip_fragment_scratch_bytes.argtypes = [ctypes.c_uint64]
+            L.pptk_ip_fragment_scratch_bytes.restype = ctypes.c_size_t
+            L.pptk_ip_fragment_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
+                                                  ctypes.c_uint32, ctypes.c_uint64,
+                                                  ctypes.c_uint32, vp, ctypes.c_uint64,
+                                                  ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.pptk_ip_fragment_device.restype = ctypes.c_int
+            L.pptk_ip_fragment_host.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp,
+                                                ctypes.c_uint64, ctypes.c_uint32, vp, vp]
+            L.pptk_ip_fragment_host.restype = ctypes.c_int
         if hasattr(L, "pptk_rx_permit_device"):        # absent from older A/B builds
             L.pptk_rx_permit_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
             L.pptk_rx_permit_scratch_bytes.restype = ctypes.c_size_t
@@ -679,6 +691,48 @@ class RxContext:
         if rc != 0:
             raise OSError(-rc, f"pptk_tcp_mss_clamp_device failed ({rc})")
 
+    def ip_fragment_device(self, frames, n, mtu, out_cap, off=None, lens=None, stride=0,
+                           fixed_len=0, out=None, out_stride=0, out_len=None, out_src=None,
+                           first=None, count=None, status=None, totals=None, scratch=None,
+                           stream=None):
+        """IPv4 fragmentation to `mtu` (pptk_ip_fragment_device), asynchronous.
+        Allocates what is not given -- out ((out_cap, out_stride) uint8,
+        out_stride = round_up(18 + mtu, 16) unless given), out_len (int16),
+        out_src / first / count (int32), status (uint8), totals (2 x int64),
+        scratch -- and returns them as a dict.  Rows [0, totals[1]) of out
+        hold the fragments; the views are the C arrays' bits (out_len is
+        uint16 in C)."""
+        import torch
+        dev = frames.device
+        out_stride = out_stride or (18 + mtu + 15) & ~15
+        if out is None:
+            out = torch.empty((out_cap, out_stride), dtype=torch.uint8, device=dev)
+        if out_len is None:
+            out_len = torch.empty(out_cap, dtype=torch.int16, device=dev)
+        if out_src is None:
+            out_src = torch.empty(out_cap, dtype=torch.int32, device=dev)
+        if first is None:
+            first = torch.empty(n, dtype=torch.int32, device=dev)
+        if count is None:
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+        if totals is None:
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+        if scratch is None:
+            scratch = torch.empty(self._L.pptk_ip_fragment_scratch_bytes(n), dtype=torch.uint8,
+                                  device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        rc = self._L.pptk_ip_fragment_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
+                                             fixed_len, n, mtu, _dp(out), out_stride, out_cap,
+                                             _dp(out_len), _dp(out_src), _dp(first), _dp(count),
+                                             _dp(status), _dp(totals), _dp(scratch),
+                                             ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_ip_fragment_device failed ({rc})")
+        return dict(out=out, out_stride=out_stride, out_len=out_len, out_src=out_src, first=first,
+                    count=count, status=status, totals=totals, scratch=scratch)
+
     # ---- multi-GPU (RCCL) -------------------------------------------------
     def comm_create(self, nranks, rank, uid):
         """Join communicator `uid` (bytes from comm_uid()) as rank/nranks."""
@@ -815,6 +869,22 @@ class RxContext:
 
     def pending_host(self):
         return self._L.pptk_rx_batch_pending(self._ctx)
+
+
+def ip_fragment_host(frame, mtu, out_cap, out_stride=0, lib_path=None):
+    """pptk_ip_fragment_host on one frame (bytes): (count, status, out,
+    out_len) with out an (out_cap, out_stride) uint8 array pre-filled with
+    0xEE whose rows [0, count) hold the fragments unless status has NOROOM."""
+    L = lib(lib_path)
+    out_stride = out_stride or (18 + mtu + 15) & ~15
+    out = np.full((max(out_cap, 1), out_stride), 0xEE, np.uint8)
+    out_len = np.zeros(max(out_cap, 1), np.uint16)
+    status = ctypes.c_uint8(0)
+    rc = L.pptk_ip_fragment_host(bytes(frame), len(frame), mtu, out.ctypes.data, out_stride,
+                                 out_cap, out_len.ctypes.data, ctypes.byref(status))
+    if rc < 0:
+        raise OSError(-rc, f"pptk_ip_fragment_host failed ({rc})")
+    return rc, status.value, out[:out_cap], out_len[:out_cap]
 
 
 def comm_uid(lib_path=None):
