@@ -347,7 +347,15 @@ int main(int argc, char **argv)
   if (rc != 0) {
     fprintf(stderr, "%s: %d\n", g_join_threads ? "pptk_rx_comm_uid" : "pptk_rx_comm_create_all",
             rc);
-    return 1;
+    /* A creation that gave up at its deadline (-ETIMEDOUT) leaves RCCL's init
+     * running in the library's helper thread: returning from main would run
+     * the HIP and RCCL library destructors under it (see the end of main).
+     * Report the failure and leave without them. */
+    printf("rx_multigpu: %d ranks on %d GPUs, %u frames, no communicator, FAILED\n", g_nranks,
+           g_nranks < ndev ? g_nranks : ndev, set.h.n);
+    fflush(stdout);
+    fflush(stderr);
+    _exit(1);
   }
   for (i = 0; i < nr; i++) {
     if (pthread_create(&pth[i], NULL, thrfn, &thr[i]) != 0) {

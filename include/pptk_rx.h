@@ -225,7 +225,14 @@ int pptk_rx_unregister_ring(struct pptk_rx_ctx *ctx, void *base);
  * the fragment side record of every frame (struct pptk_rx_frag).
  * The frame buffer must stay readable up to the next 16-byte boundary past
  * the last frame (any hipMalloc allocation is); the 16-byte chunk holding
- * the start of an empty (0-byte) frame is read too. */
+ * the start of an empty (0-byte) frame is read too.  The kernels of every
+ * device entry point that takes this layout (this one, pptk_tx_cksum_device,
+ * pptk_tx_rewrite_device, pptk_tcp_mss_clamp_device) lay their 16-byte
+ * chunks out from d_frames, not from address 0: the boundary meant is the
+ * next multiple of 16 bytes counted from d_frames, which for a d_frames
+ * that is not itself 16-byte aligned lies up to 15 bytes past the next
+ * aligned address (a d_frames inside a hipMalloc allocation with 16 bytes
+ * of slack behind the last frame is always fine). */
 struct pptk_rx_dev_batch {
   const uint8_t *d_frames;
   const uint64_t *d_off;  /* nullable: fixed stride                       */

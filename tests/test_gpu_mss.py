@@ -3,7 +3,9 @@ reference's tcp_parse_options + tcp_set_mss_cksum_update
 (tests/golden/mss.npz), byte for byte with the per-frame status, at several
 buffer misalignments; against the oracle on fresh random batches in both
 layouts; and, on a large batch, the property that clamping keeps every TCP
-checksum verdict of the receive transform.  Needs an MI355X."""
+checksum verdict of the receive transform.  The deliberate sweep of frame
+placement, option-list shapes and the fast / rare path boundary is
+test_gpu_hdr_sweep.py.  Needs an MI355X."""
 import numpy as np
 import pytest
 

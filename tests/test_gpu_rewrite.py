@@ -4,7 +4,9 @@ ip_set_src/dst_cksum_update / tcp/udp_set_src/dst_port_cksum_update
 (tests/golden/rewrite.npz), byte for byte with the per-frame status, in
 both layouts and misaligned; and, on a large batch, the size-independent
 property that a rewrite keeps every checksum verdict of the receive
-transform while the records show the new addresses and ports.  Needs an
+transform while the records show the new addresses and ports.  The
+deliberate sweep of image / chunk geometry, checksum corner values and
+random batches against the oracle is test_gpu_hdr_sweep.py.  Needs an
 MI355X."""
 import numpy as np
 import pytest
