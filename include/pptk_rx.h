@@ -437,6 +437,79 @@ int pptk_tcp_mss_clamp_device(struct pptk_rx_ctx *ctx, uint8_t *d_frames, const 
                               uint64_t n, uint16_t mss, uint32_t flags, uint8_t *d_status,
                               void *stream);
 
+/* TCP sequence-space translation (SYN proxy / TCP splice): the rewrite a
+ * stateful middlebox does on every packet of an established flow, reference
+ * iphdr/ipcksum.h:395-623 and iphdr/iphdr.c:134-246.  Frame i takes the
+ * translation d_xl[0] or d_xl[i] (d_idx NULL: xl_count must be 1 or n, as
+ * pptk_tx_rewrite_device) or d_xl[d_idx[i]] (the result of a flow-table
+ * lookup); an index >= xl_count (use 0xffffffff) means "no flow": the frame
+ * is neither read nor written and its status is PPTK_SEQ_ST_NOFLOW.
+ * Subjects are the frames whose receive record would be PPTK_RX_F_PARSED,
+ * not MALFORMED, PPTK_RX_F_L4 and proto 6 (IPv4 or IPv6, with or without a
+ * VLAN tag, never a fragment); everything else is left untouched with status
+ * 0.  With end = tcp_data_offset, a subject with end < 20 or l4_off + end
+ * past the L4 end is left untouched with status BADOPT, whatever the ops.
+ * Otherwise the status gets TCP and the requested ops are applied in this
+ * fixed order, byte for byte as the kept functions (include/ipcksum.h,
+ * include/iphdr.h) called in this order on the TCP header:
+ *   1 SEQ      tcp_set_seq_number_cksum_update(seq + seq_add)
+ *   2 ACK      tcp_set_ack_number_cksum_update(ack + ack_add), only when the
+ *              header's ACK flag is set (this API's own guard: the ack field
+ *              of a segment without ACK carries nothing)
+ *   3 SACK     tcp_find_sack_ts_headers, tcp_adjust_sack_cksum_update_2
+ *              (sack_add): the LAST SACK option of that walk
+ *   4 TSVAL    tcp_adjust_tsval_cksum_update(tsval_add)   (the same walk)
+ *   5 TSECHO   tcp_adjust_tsecho_cksum_update(tsecho_add)
+ *   6 SACK_OFF tcp_find_sack_header, tcp_disable_sack_cksum_update: the
+ *              FIRST SACK option of that other walk becomes NOPs
+ * with the checksum updated in exactly that sequence of ip_update_cksum16/32
+ * steps.  Where the reference never returns, the kept functions decide: a
+ * SACK or timestamp option with length byte 0 stops the walk, which keeps
+ * what it recorded, and a SACK option of 10 or more bytes at an odd TCP
+ * offset has each block adjusted once.  A checksum word that straddles the
+ * end of the options takes the byte past them as 0 (it cancels in the
+ * update) and never reads or writes it.  d_status (nullable) receives per
+ * frame PPTK_SEQ_ST_* bits.  Layout arguments, asynchrony and error returns
+ * as for pptk_tcp_mss_clamp_device; -EINVAL also for a null d_xl, xl_count
+ * 0, or (without d_idx) xl_count neither 1 nor n. */
+struct pptk_seqxlate {          /* 24 bytes, one per flow or per frame */
+  uint32_t ops;                 /* PPTK_SEQ_* */
+  uint32_t seq_add;             /* added to the sequence number        */
+  uint32_t ack_add;             /* added to the acknowledgement number */
+  uint32_t sack_add;            /* added to every SACK block edge      */
+  uint32_t tsval_add;           /* added to the timestamp value        */
+  uint32_t tsecho_add;          /* added to the timestamp echo reply   */
+};
+#define PPTK_SEQ_SEQ      0x01u
+#define PPTK_SEQ_ACK      0x02u
+#define PPTK_SEQ_SACK     0x04u
+#define PPTK_SEQ_TSVAL    0x08u
+#define PPTK_SEQ_TSECHO   0x10u
+#define PPTK_SEQ_SACK_OFF 0x20u
+
+#define PPTK_SEQ_ST_TCP      0x01u  /* TCP header and option area inside the segment       */
+#define PPTK_SEQ_ST_SEQ      0x02u  /* sequence number rewritten                           */
+#define PPTK_SEQ_ST_ACK      0x04u  /* acknowledgement number rewritten                    */
+#define PPTK_SEQ_ST_SACK     0x08u  /* a SACK option was found and its blocks adjusted     */
+#define PPTK_SEQ_ST_TS       0x10u  /* a timestamp option was found and adjusted           */
+#define PPTK_SEQ_ST_SACK_OFF 0x20u  /* a SACK option was overwritten with NOPs             */
+#define PPTK_SEQ_ST_BADOPT   0x40u  /* data offset < 20 or past the segment: untouched     */
+#define PPTK_SEQ_ST_NOFLOW   0x80u  /* d_idx[i] >= xl_count: untouched                     */
+
+int pptk_tcp_seq_translate_device(struct pptk_rx_ctx *ctx, uint8_t *d_frames,
+                                  const uint64_t *d_off, const uint16_t *d_len, uint64_t stride,
+                                  uint32_t fixed_len, uint64_t n,
+                                  const struct pptk_seqxlate *d_xl, uint64_t xl_count,
+                                  const uint32_t *d_idx, uint8_t *d_status, void *stream);
+
+/* The same rules on one TCP segment the caller has located (host, per
+ * packet): bytes [0, seglen) of tcphdr must be readable and writable, no
+ * byte at or past seglen is read.  Does the end < 20 || end > seglen check
+ * and the ACK-flag guard; returns the PPTK_SEQ_ST_* bits (TCP, SEQ, ACK,
+ * SACK, TS, SACK_OFF or BADOPT). */
+uint32_t pptk_tcp_seq_translate_hdr(void *tcphdr, uint32_t seglen,
+                                    const struct pptk_seqxlate *x);
+
 /* IPv4 fragmentation to an egress MTU (forwarder / tunnel ingress), the
  * batch form of the reference's fragment4() (ipfrag/ipfrag.c:11-123) with
  * the plan "as few fragments as possible".  `mtu` (68..65535) counts the IP

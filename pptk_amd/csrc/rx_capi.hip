@@ -943,6 +943,35 @@ int pptk_tcp_mss_clamp_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const ui
   return hip_err(launch_mss_clamp(a, grid, (hipStream_t)stream));
 }
 
+int pptk_tcp_seq_translate_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_t *d_off,
+                                  const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
+                                  uint64_t n, const struct pptk_seqxlate *d_xl, uint64_t xl_count,
+                                  const uint32_t *d_idx, uint8_t *d_status, void *stream) {
+  if (!c || n > 0xffffffffull) return -EINVAL;
+  if (n == 0) return 0;
+  if (!d_frames || !d_xl || xl_count == 0 || (!d_idx && xl_count != 1 && xl_count != n) ||
+      (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535))
+    return -EINVAL;
+  DeviceScope dg(c->device);
+  if (!dg.ok) return -EIO;
+  SeqKArgs a;
+  a.frames = d_frames;
+  a.frames_w = d_frames;
+  a.off = d_off;
+  a.len = d_len;
+  a.stride = stride;
+  a.n = n;
+  a.xl = d_xl;
+  a.xl_count = xl_count;
+  a.idx = d_idx;
+  a.status = d_status;
+  a.fixed_len = fixed_len;
+  a.xl_one = !d_idx && xl_count == 1 ? 1u : 0u;
+  const uint64_t blocks = (n + 255) / 256;
+  const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)c->ncu * 8);
+  return hip_err(launch_seq_translate(a, grid, (hipStream_t)stream));
+}
+
 // The length groups of the mixed path: kGroupMaxLen, or (A/B experiment)
 // PPTK_RX_BIN_BOUNDS="b0,b1", non-decreasing upper bounds of groups 0 and 1
 // (equal neighbours leave a group empty; it is not launched).

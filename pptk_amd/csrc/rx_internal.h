@@ -169,6 +169,25 @@ hipError_t launch_tx_apply(const uint64_t *txside, uint8_t *frames, const uint64
                            uint64_t stride, uint64_t n, hipStream_t s);
 hipError_t launch_rewrite(const RxKArgs &a, int grid, hipStream_t s);
 hipError_t launch_mss_clamp(const RxKArgs &a, int grid, hipStream_t s);
+
+// Arguments of the sequence-space translation kernel
+// (pptk_tcp_seq_translate_device): its own small struct, so that RxKArgs --
+// and with it the receive kernels' argument layout -- stays as it is.
+struct SeqKArgs {
+  const uint8_t *frames;
+  uint8_t *frames_w;
+  const uint64_t *off;   // nullable -> fixed stride
+  const uint16_t *len;   // nullable -> fixed_len
+  uint64_t stride;
+  uint64_t n;
+  const pptk_seqxlate *xl;
+  uint64_t xl_count;
+  const uint32_t *idx;   // nullable -> xl[xl_one ? 0 : i]
+  uint8_t *status;       // nullable
+  uint32_t fixed_len;
+  uint32_t xl_one;
+};
+hipError_t launch_seq_translate(const SeqKArgs &a, int grid, hipStream_t s);
 int rx_variant_blocks_per_cu(int variant);
 
 // Stable counting sort of 0..n-1 into kGroups length groups.  After it,

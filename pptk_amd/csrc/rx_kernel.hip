@@ -1994,6 +1994,248 @@ __global__ __launch_bounds__(256) void rx_mss_kernel(RxKArgs a) {
   }
 }
 
+// TCP sequence-space translation (pptk_tcp_seq_translate_device): one lane
+// per frame, the frame's first eight aligned chunks in the lane's LDS slot
+// and the receive transform's parse, as rx_mss_kernel.  The ops of the
+// frame's translation are then applied to the TCP header where it lies in
+// LDS -- in the slot itself when the whole header [t, t + end) is in the
+// image, else in a copy gathered at the slot's start through the FrameView
+// rare path (IPv6 extension chains, IHL 15 behind a VLAN tag) -- with the
+// checksum carried in a register through the kept functions' exact sequence
+// of ip_update_cksum16/32 steps (include/ipcksum.h: steps that leave the
+// value alone are kept too, they can turn 0xffff into 0).  A frame changes
+// up to ~50 bytes (seq, ack, checksum, four SACK blocks, the timestamps), so
+// the patched image goes back as whole 16-byte chunks where a chunk lies
+// inside the frame and byte by byte where it reaches outside it (those bytes
+// may be a neighbour's): FieldWriter's rule, with the changed bytes kept as
+// a mask over the header's 60 bytes instead of the slot's 128.
+struct SeqPatch {
+  LDS_AS uint8_t *h;     // TCP header bytes [0, end) in LDS
+  int end;
+  uint32_t ck;
+  uint64_t touched = 0;  // header byte positions written
+
+  // a byte past the options is taken as 0: it only ever is the far half of
+  // a straddling checksum word, where it cancels (and is never written)
+  __device__ __forceinline__ uint32_t u8(int k) const { return k < end ? (uint32_t)h[k] : 0u; }
+  __device__ __forceinline__ uint32_t be16(int k) const { return (u8(k) << 8) | u8(k + 1); }
+  __device__ __forceinline__ uint32_t be32(int k) const { return (be16(k) << 16) | be16(k + 2); }
+  __device__ __forceinline__ void put(int k, uint32_t v, int nbytes) {
+    for (int b = 0; b < nbytes; ++b) {
+      h[k + b] = (uint8_t)(v >> (8 * (nbytes - 1 - b)));
+      touched |= 1ull << (k + b);
+    }
+  }
+  // tcp_set_seq/ack_number_cksum_update (ipcksum.h): fields at offsets 4, 8
+  __device__ __forceinline__ void add_aligned32(int k, uint32_t add) {
+    const uint32_t o = be32(k), nw = o + add;
+    ck = upd32(ck, o, nw);
+    put(k, nw, 4);
+  }
+  // pptk_tcp_adjust_ts32: a 32-bit field at any offset; at an odd one the
+  // three words that straddle it, old values read before the write
+  __device__ __forceinline__ void add_ts32(int f, uint32_t add) {
+    const uint32_t o = be32(f), nw = o + add;
+    if (!(f & 1)) {
+      ck = upd32(ck, o, nw);
+    } else {
+      const uint32_t x0 = u8(f - 1), x1 = u8(f + 4);
+      ck = upd16(ck, (x0 << 8) | (o >> 24), (x0 << 8) | (nw >> 24));
+      ck = upd16(ck, (o >> 8) & 0xffffu, (nw >> 8) & 0xffffu);
+      ck = upd16(ck, ((o & 0xffu) << 8) | x1, ((nw & 0xffu) << 8) | x1);
+    }
+    put(f, nw, 4);
+  }
+  // tcp_adjust_sack_cksum_update: every 8-byte block from option offset 2,
+  // each adjusted once (at most 4: sacklen <= 40)
+  __device__ __forceinline__ void adjust_sack(int so, int sl, uint32_t add) {
+    for (int k = 2; k + 8 <= sl; k += 8) {
+      const int p = so + k;
+      const uint32_t s0 = be32(p), e0 = be32(p + 4), s1 = s0 + add, e1 = e0 + add;
+      if (!(so & 1)) {
+        ck = upd32(ck, s0, s1);
+        ck = upd32(ck, e0, e1);
+      } else {
+        const uint32_t x0 = u8(p - 1), x1 = u8(p + 8);
+        ck = upd16(ck, (x0 << 8) | (s0 >> 24), (x0 << 8) | (s1 >> 24));
+        ck = upd32(ck, (s0 << 8) | (e0 >> 24), (s1 << 8) | (e1 >> 24));
+        ck = upd32(ck, (e0 << 8) | x1, (e1 << 8) | x1);
+      }
+      put(p, s1, 4);
+      put(p + 4, e1, 4);
+    }
+  }
+  // tcp_disable_sack_cksum_update: NOPs pair by pair (at most 20 pairs); an
+  // odd last byte shares its word with the byte behind the option, which
+  // stays
+  __device__ __forceinline__ void disable_sack(int so, int sl) {
+    for (int k = 0; k + 1 <= sl; k += 2) {
+      const bool whole = k + 2 <= sl;
+      const int p = so + k;
+      const uint32_t o = be16(p);
+      const uint32_t nw = whole ? 0x0101u : ((o & 0xffu) | 0x0100u);
+      if (!(so & 1)) {
+        ck = upd16(ck, o, nw);
+      } else {
+        const uint32_t x0 = u8(p - 1), x1 = u8(p + 2);
+        ck = upd16(ck, (x0 << 8) | (o >> 8), (x0 << 8) | (nw >> 8));
+        ck = upd16(ck, ((o & 0xffu) << 8) | x1, ((nw & 0xffu) << 8) | x1);
+      }
+      put(p, nw >> (whole ? 0 : 8), whole ? 2 : 1);
+      if (!whole) break;
+    }
+  }
+};
+
+constexpr int SEQ_SLOT = 128;
+#ifdef PPTK_SEQ_BYTE_STORES
+constexpr bool kSeqByteStores = true;
+#else
+constexpr bool kSeqByteStores = false;
+#endif
+
+__global__ __launch_bounds__(256) void rx_seq_kernel(SeqKArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[256 * (SEQ_SLOT + 4)];
+  LDS_AS uint8_t *slot = (LDS_AS uint8_t *)lds + threadIdx.x * (SEQ_SLOT + 4);
+  const uint64_t step = (uint64_t)gridDim.x * 256u;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.n; i += step) {
+    const uint64_t j = a.idx ? (uint64_t)a.idx[i] : (a.xl_one ? 0u : i);
+    if (j >= a.xl_count) {   // no flow: the frame is not even read
+      if (a.status) a.status[i] = (uint8_t)PPTK_SEQ_ST_NOFLOW;
+      continue;
+    }
+    const uint64_t base = a.off ? a.off[i] : i * a.stride;
+    const uint32_t len = a.len ? a.len[i] : a.fixed_len;
+    const int m = (int)(base & 15);
+    const int nch = max((m + (int)len + 15) >> 4, 1);
+    park_chunks<SEQ_SLOT>(slot, (const u32x4 *)(a.frames + (base - (uint64_t)m)), nch);
+    const FrameView v = {slot, (const GLB_AS uint8_t *)a.frames + base, m, SEQ_SLOT - m};
+    const Parse p = parse_frame(v, len);
+    uint32_t st = 0;
+    if ((p.flags & (PPTK_RX_F_PARSED | PPTK_RX_F_MALFORMED | PPTK_RX_F_L4)) ==
+            (PPTK_RX_F_PARSED | PPTK_RX_F_L4) &&
+        p.proto == 6) {
+      const int t = (int)p.rs;   // TCP header
+      const int end = (int)(v.u8(t + 12) >> 4) * 4;   // tcp_data_offset
+      if (end < 20 || t + end > (int)p.re) {
+        st = PPTK_SEQ_ST_BADOPT;
+      } else {
+        st = PPTK_SEQ_ST_TCP;
+        const pptk_seqxlate x = a.xl[j];
+        const bool fast = m + t + end <= SEQ_SLOT;
+        if (!fast) {
+          // gather the header at the slot's start: byte k comes from image
+          // position m + t + k > k or from global memory, so the ascending
+          // copy never overwrites a byte it has yet to read
+          for (int k = 0; k < end; ++k) slot[k] = (uint8_t)v.u8(t + k);
+        }
+        SeqPatch s{fast ? slot + m + t : slot, end, 0u};
+        const uint32_t ck0 = s.be16(16);
+        s.ck = ck0;
+        if (x.ops & PPTK_SEQ_SEQ) {
+          s.add_aligned32(4, x.seq_add);
+          st |= PPTK_SEQ_ST_SEQ;
+        }
+        if ((x.ops & PPTK_SEQ_ACK) && (s.u8(13) & 0x10u)) {
+          s.add_aligned32(8, x.ack_add);
+          st |= PPTK_SEQ_ST_ACK;
+        }
+        if (x.ops & (PPTK_SEQ_SACK | PPTK_SEQ_TSVAL | PPTK_SEQ_TSECHO | PPTK_SEQ_SACK_OFF)) {
+          // tcp_find_sack_ts_headers (last SACK, last 10-byte timestamp) and
+          // tcp_find_sack_header (first SACK) in one pass: the two walks step
+          // through the same offsets until the second one ends -- at the
+          // first SACK option, or where a timestamp option has a length
+          // below 2, which only the first walk steps over (`first_done`);
+          // kind 0, and any other kind with a length below 2, end both.
+          // The offset grows by at least 1 per step from 20 to at most 60:
+          // 40 steps bound the loop whatever the bytes are.  No op writes a
+          // byte a walk reads (kinds and lengths stay), so walking once
+          // before the ops equals the kept functions' walks between them.
+          int off = 20, sackoff = 0, sacklen = 0, tsoff = 0, first = 0, firstlen = 0;
+          bool first_done = false;
+          for (int n = 0; n < 40 && off < end; ++n) {
+            const uint32_t kind = s.u8(off);
+            if (kind == 0) break;
+            if (kind == 1) {
+              off++;
+              continue;
+            }
+            const int left = end - off;
+            const int lb = (int)s.u8(off + 1);
+            const int L = (off + 1 < end && lb < left) ? lb : left;
+            if (kind == 5) {
+              sackoff = off;
+              sacklen = L;
+              if (!first_done) {
+                first = off;
+                firstlen = L;
+                first_done = true;
+              }
+            } else if (kind == 8) {
+              if (L == 10) tsoff = off;
+              if (L < 2) first_done = true;
+            } else if (L < 2) {
+              break;
+            }
+            if (L == 0) break;
+            off += L;
+          }
+          if ((x.ops & PPTK_SEQ_SACK) && sackoff) {
+            s.adjust_sack(sackoff, sacklen, x.sack_add);
+            st |= PPTK_SEQ_ST_SACK;
+          }
+          if (tsoff) {
+            if (x.ops & PPTK_SEQ_TSVAL) s.add_ts32(tsoff + 2, x.tsval_add);
+            if (x.ops & PPTK_SEQ_TSECHO) s.add_ts32(tsoff + 6, x.tsecho_add);
+            if (x.ops & (PPTK_SEQ_TSVAL | PPTK_SEQ_TSECHO)) st |= PPTK_SEQ_ST_TS;
+          }
+          if ((x.ops & PPTK_SEQ_SACK_OFF) && first) {
+            s.disable_sack(first, firstlen);
+            st |= PPTK_SEQ_ST_SACK_OFF;
+          }
+        }
+        if (s.ck != ck0) s.put(16, s.ck, 2);
+        if (s.touched) {
+          GLB_AS uint8_t *fw = (GLB_AS uint8_t *)a.frames_w + base;
+          if (fast) {
+            GLB_AS uint8_t *row = fw - m;
+            const int hp = m + t;   // the header's place in the slot
+#pragma unroll
+            for (int c = 0; c < SEQ_SLOT / 16; ++c) {
+              // the changed bytes of chunk c: header bytes [16c - hp, +16)
+              const int lo = 16 * c - hp;
+              uint32_t tb = lo >= 64 || lo <= -16 ? 0u
+                            : (uint32_t)(lo >= 0 ? s.touched >> lo : s.touched << -lo) & 0xffffu;
+              if (!tb) continue;
+              const int fo = 16 * c - m;   // frame offset of the chunk
+              // (PPTK_SEQ_BYTE_STORES: the changed bytes one by one
+              // everywhere, the A/B partner of the chunk write-back)
+              if (!kSeqByteStores && fo >= 0 && fo + 16 <= (int)len) {
+                const LDS_AS uint32_t *w = (const LDS_AS uint32_t *)slot + 4 * c;
+                *(GLB_AS u32x4 *)(row + 16 * c) = (u32x4){w[0], w[1], w[2], w[3]};
+              } else {
+                while (tb) {
+                  const int b = __builtin_ctz(tb);
+                  row[16 * c + b] = slot[16 * c + b];
+                  tb &= tb - 1;
+                }
+              }
+            }
+          } else {
+            uint64_t tb = s.touched;   // bits below `end` only: inside the frame
+            while (tb) {
+              const int b = __builtin_ctzll(tb);
+              fw[t + b] = slot[b];
+              tb &= tb - 1;
+            }
+          }
+        }
+      }
+    }
+    if (a.status) a.status[i] = (uint8_t)st;
+  }
+}
+
 // Descriptor sources of an offset-described (GATHER) launch: absent arrays
 // read the context's zeroed stand-in buffer (RxKArgs::zero).
 void gather_args(RxKArgs &a) {
@@ -2123,6 +2365,11 @@ hipError_t launch_rewrite(const RxKArgs &a, int grid, hipStream_t s) {
 
 hipError_t launch_mss_clamp(const RxKArgs &a, int grid, hipStream_t s) {
   hipLaunchKernelGGL(rx_mss_kernel, dim3(grid), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_seq_translate(const SeqKArgs &a, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(rx_seq_kernel, dim3(grid), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -33,6 +33,15 @@ RW_ST_IP, RW_ST_L4, RW_ST_TTL_ZERO, RW_ST_EXPIRED, RW_ST_ICMP = 0x1, 0x2, 0x4, 0
 RW_ICMP_ID = 0x20
 MSS_SYN_ONLY = 0x1
 MSS_ST_TCP, MSS_ST_FOUND, MSS_ST_CLAMPED, MSS_ST_BADOPT = 0x1, 0x2, 0x4, 0x8
+# struct pptk_seqxlate (pptk_tcp_seq_translate_device / _hdr): ops and the
+# per-flow offsets added to seq, ack, the SACK block edges and the timestamps
+seqxlate_dtype = np.dtype([("ops", "<u4"), ("seq_add", "<u4"), ("ack_add", "<u4"),
+                           ("sack_add", "<u4"), ("tsval_add", "<u4"), ("tsecho_add", "<u4")])
+assert seqxlate_dtype.itemsize == 24
+SEQ_SEQ, SEQ_ACK, SEQ_SACK, SEQ_TSVAL, SEQ_TSECHO, SEQ_SACK_OFF = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+(SEQ_ST_TCP, SEQ_ST_SEQ, SEQ_ST_ACK, SEQ_ST_SACK, SEQ_ST_TS, SEQ_ST_SACK_OFF, SEQ_ST_BADOPT,
+ SEQ_ST_NOFLOW) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
+SEQ_NOFLOW = 0xFFFFFFFF   # d_idx entry meaning "no flow"
 # PPTK_FRAG_ST_*: per-frame status of pptk_ip_fragment_device / _host
 (FRAG_ST_IPV4, FRAG_ST_FITS, FRAG_ST_DONE, FRAG_ST_DF, FRAG_ST_ISFRAG, FRAG_ST_BADCKSUM,
  FRAG_ST_NOROOM) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40

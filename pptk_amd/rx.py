@@ -178,7 +178,8 @@ EXPORTS = ("pptk_rx_opts_default", "pptk_rx_ctx_create", "pptk_rx_ctx_destroy",
            "pptk_rx_permit_scratch_bytes", "pptk_rx_permit_device", "pptk_rx_permit_keys_device",
            "pptk_rx_permit_status", "pptk_rx_tokens_refill_device", "pptk_tx_cksum_device", "pptk_tx_set_side_buffer",
            "pptk_tx_rewrite_device",
-           "pptk_tcp_mss_clamp_device", "pptk_ip_fragment_scratch_bytes",
+           "pptk_tcp_mss_clamp_device", "pptk_tcp_seq_translate_device",
+           "pptk_tcp_seq_translate_hdr", "pptk_ip_fragment_scratch_bytes",
            "pptk_ip_fragment_device", "pptk_ip_fragment_host", "pptk_rx_autotune", "pptk_rx_place_records",
            "pptk_rx_place_buffers", "pptk_rx_ring_alloc", "pptk_rx_ring_free",
            "pptk_rx_gather_alloc", "pptk_rx_gather_free",
@@ -279,6 +280,13 @@ def lib(path=None):
                                                     ctypes.c_uint32, ctypes.c_uint64,
                                                     ctypes.c_uint16, ctypes.c_uint32, vp, vp]
             L.pptk_tcp_mss_clamp_device.restype = ctypes.c_int
+        if hasattr(L, "pptk_tcp_seq_translate_device"):   # absent from older A/B builds
+            L.pptk_tcp_seq_translate_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
+                                                        ctypes.c_uint32, ctypes.c_uint64, vp,
+                                                        ctypes.c_uint64, vp, vp, vp]
+            L.pptk_tcp_seq_translate_device.restype = ctypes.c_int
+            L.pptk_tcp_seq_translate_hdr.argtypes = [vp, ctypes.c_uint32, vp]
+            L.pptk_tcp_seq_translate_hdr.restype = ctypes.c_uint32
         if hasattr(L, "pptk_ip_fragment_device"):      # absent from older A/B builds
             L.pptk_ip_fragment_scratch_bytes.argtypes = [ctypes.c_uint64]
             L.pptk_ip_fragment_scratch_bytes.restype = ctypes.c_size_t
@@ -691,6 +699,26 @@ class RxContext:
         if rc != 0:
             raise OSError(-rc, f"pptk_tcp_mss_clamp_device failed ({rc})")
 
+    def seq_translate_device(self, frames, n, xl, idx=None, off=None, lens=None, stride=0,
+                             fixed_len=0, status=None, stream=None):
+        """TCP sequence-space translation (pptk_tcp_seq_translate_device), in
+        place and asynchronously.  xl: torch uint8 CUDA tensor of struct
+        pptk_seqxlate entries (24 bytes each, records.seqxlate_dtype): 1 or n
+        of them, or a flow table indexed by idx (torch int32 CUDA tensor of n
+        entries, -1 = 0xffffffff = no flow); status: optional torch uint8
+        CUDA tensor of n PPTK_SEQ_ST_* bytes."""
+        import torch
+        if not hasattr(self._L, "pptk_tcp_seq_translate_device"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_tcp_seq_translate_device")
+        count = xl.numel() * xl.element_size() // 24
+        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+        rc = self._L.pptk_tcp_seq_translate_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
+                                                   stride, fixed_len, n, _dp(xl), count,
+                                                   _dp(idx), _dp(status),
+                                                   ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_tcp_seq_translate_device failed ({rc})")
+
     def ip_fragment_device(self, frames, n, mtu, out_cap, off=None, lens=None, stride=0,
                            fixed_len=0, out=None, out_stride=0, out_len=None, out_src=None,
                            first=None, count=None, status=None, totals=None, scratch=None,
@@ -885,6 +913,23 @@ def ip_fragment_host(frame, mtu, out_cap, out_stride=0, lib_path=None):
     if rc < 0:
         raise OSError(-rc, f"pptk_ip_fragment_host failed ({rc})")
     return rc, status.value, out[:out_cap], out_len[:out_cap]
+
+
+def tcp_seq_translate_hdr(segment_bytes, xl, lib_path=None):
+    """pptk_tcp_seq_translate_hdr on one TCP segment (bytes, the TCP header
+    first) with the translation xl (one records.seqxlate_dtype entry, or its
+    24 bytes): (status, the segment's bytes afterwards)."""
+    L = lib(lib_path)
+    if not hasattr(L, "pptk_tcp_seq_translate_hdr"):
+        raise OSError(38, "this libpptkrx.so lacks pptk_tcp_seq_translate_hdr")
+    x = np.frombuffer(xl.tobytes() if hasattr(xl, "tobytes") else bytes(xl), np.uint8)
+    if x.size != 24:
+        raise ValueError("xl must be one struct pptk_seqxlate (24 bytes)")
+    # a buffer of exactly len(segment) bytes (at least one, to have an address)
+    seg = np.frombuffer(bytes(segment_bytes), np.uint8).copy()
+    buf = seg if seg.size else np.zeros(1, np.uint8)
+    st = L.pptk_tcp_seq_translate_hdr(buf.ctypes.data, seg.size, x.ctypes.data)
+    return st, seg.tobytes()
 
 
 def comm_uid(lib_path=None):
