@@ -177,6 +177,26 @@ static inline uint16_t udp_cksum(const void *l4) { return hdr_get16n(PPTK_AT(l4,
  * stored big-endian. */
 #define PPTK_W(p, k) ((unsigned char *)(p) + (k))
 static inline void ip_set_ttl(void *pkt, uint8_t ttl) { *PPTK_W(pkt, 8) = ttl; }
+/* header construction (a tunnel's outer header, ldp/ldptunnel.c:29-46):
+ * iphdr.h:379-389 (address pointers), 409-413 (ethertype), 867-874 (version),
+ * 895-907 (header length), 1193-1197 (protocol).  ip_set_version and
+ * ip_set_hdr_len each leave the other nibble of byte 0 as it was;
+ * ip_set_hdr_len abort()s on a length that is not a multiple of 4, as the
+ * reference does. */
+static inline void *ether_dst(void *pkt) { return PPTK_W(pkt, 0); }
+static inline void *ether_src(void *pkt) { return PPTK_W(pkt, 6); }
+static inline void ether_set_type(void *pkt, uint16_t type) { hdr_set16n(PPTK_W(pkt, 12), type); }
+static inline void ip_set_version(void *pkt, uint8_t version)
+{
+  *PPTK_W(pkt, 0) = (unsigned char)((*PPTK_AT(pkt, 0) & 0x0f) | ((version & 0xf) << 4));
+}
+static inline void ip_set_hdr_len(void *pkt, uint8_t hdr_len)
+{
+  if (hdr_len % 4 != 0)
+    abort();
+  *PPTK_W(pkt, 0) = (unsigned char)((*PPTK_AT(pkt, 0) & 0xf0) | ((hdr_len / 4) & 0xf));
+}
+static inline void ip_set_proto(void *pkt, uint8_t proto) { *PPTK_W(pkt, 9) = proto; }
 /* fragmentation fields: iphdr.h:949-953 (total length), 1099-1103 (id),
  * 1130-1144 (offset), 1029-1038, 1046-1055, 1076-1091 (the three flag bits),
  * 1283-1286 (payload).  ip_set_frag_off abort()s on an offset that is not a

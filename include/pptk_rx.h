@@ -590,6 +590,138 @@ int pptk_ip_fragment_host(const void *frame, uint32_t len, uint32_t mtu, uint8_t
                           uint64_t out_stride, uint32_t out_cap, uint16_t *out_len,
                           uint8_t *status);
 
+/* GRE tunnel gateway (tunnel ingress and egress), the batch form of the
+ * reference's ldp/ldptunnel.c: encap puts the fixed 38-byte header Ethernet +
+ * IPv4 + GRE with protocol type 0x6558 (transparent Ethernet bridging) in
+ * front of every frame (template :29-46, per packet :126-128), decap finds
+ * the inner frame of such a packet (:155-158).  With them a tunnel endpoint
+ * runs  decap -> pptk_rx_batch_device on the inner frames  and
+ * pptk_tcp_mss_clamp_device -> encap -> pptk_ip_fragment_device  on batches
+ * that stay in device memory.
+ *
+ * Encap.  Frame i takes the tunnel d_tun[0] or d_tun[i] (d_idx NULL:
+ * tun_count must be 1 or n) or d_tun[d_idx[i]]; an index >= tun_count (use
+ * 0xffffffff) means "no tunnel": status PPTK_TUN_ST_NOFLOW, the frame is not
+ * read and its slot is not written.  A tunnel whose `reserved` is not 0 or
+ * whose `flags` hold an unknown bit is malformed and gives its frames
+ * PPTK_TUN_ST_BADTUN, likewise unread and unwritten: the device call cannot
+ * look into d_tun without waiting for the stream, so that check is per frame
+ * and not an error return (a caller that builds the table on the host checks
+ * it there; the Python binding does).  Slot i, at d_out +
+ * i * out_stride, belongs to frame i: no compaction, one launch.  Per frame,
+ * with len its length:
+ *   len < 14                PPTK_TUN_ST_RUNT: nothing is read
+ *   38 + len > 65535        PPTK_TUN_ST_TOOBIG (the 16-bit frame length of the
+ *                           batch layout; so len + 24 <= 65535 always holds)
+ *   38 + len > out_stride   PPTK_TUN_ST_NOROOM (host form: > out_cap); TOOBIG
+ *                           and NOROOM are independent of each other
+ *   else                    PPTK_TUN_ST_DONE: slot bytes [0, 38 + len) are
+ *                           written, bytes [38 + len, round_up(38 + len, 16))
+ *                           are zero, the rest of the slot is untouched
+ * A frame without DONE has no byte of its slot written.  d_out_len[i]
+ * (nullable) is 38 + len with DONE, else 0; d_status[i] (nullable) the
+ * PPTK_TUN_ST_* bits.  The header is what ldptunnel.c writes through the kept
+ * setters of include/iphdr.h:
+ *   Ethernet  ether_dst, ether_src, ether_set_type(0x0800)
+ *   IPv4      ip_set_version(4), ip_set_hdr_len(20), tos, ip_set_total_len(
+ *             len + 24), ip_set_id(id), ip_set_dont_frag(PPTK_TUN_DF) with MF
+ *             and offset 0, ip_set_ttl, ip_set_proto(47), ip_set_src,
+ *             ip_set_dst, ip_set_hdr_cksum_calc(ip, 20)
+ *   GRE       00 00 65 58 (no checksum, key or sequence number, version 0)
+ * followed by the len frame bytes unchanged.  id is t.id, or with
+ * PPTK_TUN_ID_SEQ (uint16_t)(t.id + id_base + i) (host form: seq in place of
+ * id_base + i), which wraps 0xffff -> 0.
+ *
+ * d_out must be 16-byte aligned, out_stride a multiple of 16, d_tun 16-byte
+ * aligned (-EINVAL otherwise); -EINVAL also for a null d_tun, tun_count 0 or
+ * (without d_idx) tun_count neither 1 nor n, as
+ * pptk_tcp_seq_translate_device.  Layout arguments, read bounds (nothing
+ * outside the aligned 16-byte chunks of [frame, frame + len) is read, no
+ * frame shorter than 14 bytes is read at all), asynchrony and the other
+ * error returns are those of pptk_ip_fragment_device; there is no scratch
+ * and no limit on n.  The slots go straight into pptk_ip_fragment_device,
+ * pptk_rx_batch_device or pptk_tx_cksum_device (stride = out_stride, d_len =
+ * d_out_len).
+ *
+ * Decap is zero-copy: it writes descriptors, never frames.  The outer subject
+ * test is pptk_ip_fragment_device's: one optional 802.1Q tag, ethertype
+ * 0x0800, version 4, 20 <= ihl <= tl, l2 + tl <= len; a subject gets
+ * PPTK_DECAP_ST_IPV4.  A subject with ip_proto 47 is checked further, each
+ * bit on its own:
+ *   ISFRAG    ip_more_frags or ip_frag_off != 0
+ *   BADCKSUM  ip_hdr_cksum_calc(ip, ihl) != 0
+ *   GRE       not ISFRAG and tl - ihl >= 4
+ *   SHORT     not ISFRAG and tl - ihl < 4
+ *   GREOPT    with GRE: the first 16-bit GRE word != 0 (C, K or S flag, a
+ *             reserved bit or a version)
+ *   PTYPE     with GRE: the second GRE word != 0x6558
+ *   OK        GRE with none of BADCKSUM, GREOPT, PTYPE
+ * With OK d_in_off[i] = base + l2 + ihl + 4, an absolute byte offset into
+ * d_frames (base = d_off[i] or i * stride), and d_in_len[i] = tl - ihl - 4:
+ * Ethernet padding after the outer packet is excluded.  Otherwise d_in_off[i]
+ * = base and d_in_len[i] = 0.  The pair goes straight into
+ * pptk_rx_batch_device as d_off / d_len.  All three outputs are nullable.
+ *
+ * Out of scope: the GRE key, sequence and checksum fields (GREOPT: the caller
+ * decides), IPv6 or IP-in-IP outers, a match of the outer addresses against
+ * an endpoint (the caller has them from the outer frames' receive records),
+ * the ICMP answer to a DF packet that does not fit, and a host ldp_packet[]
+ * batch path (the host forms are per packet). */
+struct pptk_tunnel {            /* 32 bytes, one per tunnel */
+  uint8_t eth_dst[6], eth_src[6];
+  uint32_t src, dst;            /* outer IPv4, host order (ip_set_src/dst) */
+  uint16_t id;                  /* ip_set_id */
+  uint8_t ttl, tos;
+  uint32_t flags;               /* PPTK_TUN_DF | PPTK_TUN_ID_SEQ */
+  uint32_t reserved;            /* must be 0 */
+};
+#define PPTK_TUN_DF     0x1u    /* ip_set_dont_frag(ip, 1)                 */
+#define PPTK_TUN_ID_SEQ 0x2u    /* id counts up with the frame index       */
+#define PPTK_TUN_HDR_LEN 38u    /* 14 + 20 + 4 */
+
+#define PPTK_TUN_ST_DONE   0x01u  /* slot written                             */
+#define PPTK_TUN_ST_RUNT   0x02u  /* len < 14: nothing read, nothing written  */
+#define PPTK_TUN_ST_TOOBIG 0x04u  /* 38 + len > 65535                         */
+#define PPTK_TUN_ST_NOROOM 0x08u  /* 38 + len > out_stride (host: out_cap)    */
+#define PPTK_TUN_ST_NOFLOW 0x10u  /* tunnel index >= tun_count: frame not read */
+#define PPTK_TUN_ST_BADTUN 0x20u  /* malformed tunnel entry: frame not read    */
+
+#define PPTK_DECAP_ST_IPV4     0x01u  /* a subject: parsed IPv4                */
+#define PPTK_DECAP_ST_GRE      0x02u  /* proto 47, whole, a GRE header fits    */
+#define PPTK_DECAP_ST_OK       0x04u  /* descriptor points at the inner frame  */
+#define PPTK_DECAP_ST_ISFRAG   0x08u  /* proto 47 and a fragment               */
+#define PPTK_DECAP_ST_BADCKSUM 0x10u  /* proto 47 and a bad header checksum    */
+#define PPTK_DECAP_ST_SHORT    0x20u  /* proto 47, whole, tl - ihl < 4         */
+#define PPTK_DECAP_ST_GREOPT   0x40u  /* GRE flags or version not 0            */
+#define PPTK_DECAP_ST_PTYPE    0x80u  /* GRE protocol type not 0x6558          */
+
+int pptk_tunnel_encap_device(struct pptk_rx_ctx *ctx, const uint8_t *d_frames,
+                             const uint64_t *d_off, const uint16_t *d_len, uint64_t stride,
+                             uint32_t fixed_len, uint64_t n, const struct pptk_tunnel *d_tun,
+                             uint64_t tun_count, const uint32_t *d_idx, uint32_t id_base,
+                             uint8_t *d_out, uint64_t out_stride, uint16_t *d_out_len,
+                             uint8_t *d_status, void *stream);
+int pptk_tunnel_decap_device(struct pptk_rx_ctx *ctx, const uint8_t *d_frames,
+                             const uint64_t *d_off, const uint16_t *d_len, uint64_t stride,
+                             uint32_t fixed_len, uint64_t n, uint64_t *d_in_off,
+                             uint16_t *d_in_len, uint8_t *d_status, void *stream);
+
+/* The per-packet host forms, and the CPU statement of the contract above
+ * (plain C over iphdr.h / ipcksum.h, pptk_amd/csrc/host/tunnel.c).  Both
+ * return the status bits.  Encap takes the tunnel itself (no index) and seq
+ * in place of id_base + i; out_cap is the size of `out` in bytes: NOROOM is
+ * 38 + len > out_cap, and with DONE out[0, min(round_up(38 + len, 16),
+ * out_cap)) is written.  *out_len (nullable) = 38 + len or 0.  A null t or
+ * out, or a null frame with len >= 14, gives NOFLOW, a malformed t
+ * BADTUN.  `out` needs no
+ * alignment.  Decap sets *in_off (relative to frame) and *in_len, both
+ * nullable. */
+uint32_t pptk_tunnel_encap_host(const void *frame, uint32_t len, const struct pptk_tunnel *t,
+                                uint32_t seq, uint8_t *out, uint64_t out_cap,
+                                uint16_t *out_len);
+uint32_t pptk_tunnel_decap_host(const void *frame, uint32_t len, uint32_t *in_off,
+                                uint16_t *in_len);
+
 /* Tuning: force kernel variant `variant` (0 .. pptk_rx_variant_count()-1)
  * and/or memory-policy flags for every later batch of this context; -1
  * restores the automatic choice (variant by frame length and alignment).

@@ -16,12 +16,12 @@
 // workgroup.
 #include <errno.h>
 
+#include "copy16.h"
 #include "rx_internal.h"
 
 namespace pptk {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define LDS_AS __attribute__((address_space(3)))
 
 constexpr int kTile = 256;                  // frames per plan / apply block = scan tile
@@ -70,31 +70,6 @@ ScratchLayout scratch_layout(uint64_t n) {
   l.st = l.first + up16(n * 4);
   l.total = l.st + up16(n);
   return l;
-}
-
-__device__ __forceinline__ uint32_t bswap16(uint32_t x) {
-  return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu);
-}
-
-// end-around-carry fold, as the reference's loop (iphdr/ipcksum.h:17-25)
-__device__ __forceinline__ uint32_t fold16(uint32_t s) {
-  s = (s & 0xffffu) + (s >> 16);
-  s = (s & 0xffffu) + (s >> 16);
-  return s;
-}
-
-__device__ __forceinline__ uint32_t halves(uint32_t w) { return (w & 0xffffu) + (w >> 16); }
-
-__device__ __forceinline__ uint32_t ld_u8(uintptr_t A) { return *(const uint8_t *)A; }
-
-// Four bytes at any byte address as a little-endian dword, from the one or
-// two aligned dwords that hold them (both inside the frame when the four
-// bytes are).
-__device__ __forceinline__ uint32_t ld_le32(uintptr_t A) {
-  const uint32_t *w = (const uint32_t *)(A & ~(uintptr_t)3);
-  const uint32_t r = (uint32_t)(A & 3);
-  const uint32_t lo = w[0], hi = w[r ? 1 : 0];
-  return __builtin_amdgcn_alignbyte(hi, lo, r);
 }
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
@@ -240,60 +215,7 @@ __global__ __launch_bounds__(kTile) void frag_apply_kernel(FragArgs a) {
 }
 
 // ---- emit ------------------------------------------------------------------
-// 16 bytes from any byte address A, of which only those below `lim` (> A)
-// are meaningful: the aligned chunk holding A and the aligned chunk holding
-// the last needed byte (the same or the next one), funnelled to A's
-// alignment.  Nothing outside the aligned chunks of [A, lim) is read.  The
-// loads and the funnel are separate so that a lane can have the chunks of
-// several rounds in flight before it shifts the first.
-struct Raw16 {
-  u32x4 lo, hi;
-};
-
-__device__ __forceinline__ Raw16 load16_raw(uintptr_t A, uintptr_t lim) {
-  const uintptr_t end = A + 16 < lim ? A + 16 : lim;
-  Raw16 r;
-  r.lo = __builtin_nontemporal_load((const u32x4 *)(A & ~(uintptr_t)15));
-  r.hi = __builtin_nontemporal_load((const u32x4 *)((end - 1) & ~(uintptr_t)15));
-  return r;
-}
-
-__device__ __forceinline__ u32x4 funnel16(const Raw16 &c, uintptr_t A) {
-  const uint32_t sh = (uint32_t)(A & 15), r = sh & 3u;
-  // dword select in two steps (by 2, by 1), then the byte funnel
-  const bool s2 = sh & 8u, s1 = sh & 4u;
-  const uint32_t f0 = s2 ? c.lo.z : c.lo.x, f1 = s2 ? c.lo.w : c.lo.y, f2 = s2 ? c.hi.x : c.lo.z;
-  const uint32_t f3 = s2 ? c.hi.y : c.lo.w, f4 = s2 ? c.hi.z : c.hi.x, f5 = s2 ? c.hi.w : c.hi.y;
-  const uint32_t e0 = s1 ? f1 : f0, e1 = s1 ? f2 : f1, e2 = s1 ? f3 : f2, e3 = s1 ? f4 : f3;
-  const uint32_t e4 = s1 ? f5 : f4;
-  u32x4 o;
-  o.x = __builtin_amdgcn_alignbyte(e1, e0, r);
-  o.y = __builtin_amdgcn_alignbyte(e2, e1, r);
-  o.z = __builtin_amdgcn_alignbyte(e3, e2, r);
-  o.w = __builtin_amdgcn_alignbyte(e4, e3, r);
-  return o;
-}
-
-__device__ __forceinline__ u32x4 load16(uintptr_t A, uintptr_t lim) {
-  return funnel16(load16_raw(A, lim), A);
-}
-
-// mask of the first nb bytes of a dword (nb may be <= 0 or >= 4)
-__device__ __forceinline__ uint32_t low_bytes(int nb) {
-  return nb <= 0 ? 0u : (nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u);
-}
-
-// the big-endian 16-bit field at slot offset pos (even) := val, if it lies in
-// the chunk at slot offset o
-__device__ __forceinline__ void put16(u32x4 &v, uint32_t o, uint32_t pos, uint32_t val) {
-  const uint32_t rel = pos - o;
-  if (rel >= 16) return;
-  const uint32_t sh = (rel & 3u) * 8u, le = bswap16(val) << sh, keep = ~(0xffffu << sh);
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-    if ((rel >> 2) == (uint32_t)d) v[d] = (v[d] & keep) | le;
-}
-
+// (the re-aligning chunk loads and the field helpers: copy16.h)
 __device__ __forceinline__ void emit_frame(const FragArgs &a, uint64_t i, uint32_t t,
                                            LDS_AS u32x4 *hds) {
   const uint64_t base = a.off ? a.off[i] : i * a.stride;

@@ -45,6 +45,16 @@ SEQ_NOFLOW = 0xFFFFFFFF   # d_idx entry meaning "no flow"
 # PPTK_FRAG_ST_*: per-frame status of pptk_ip_fragment_device / _host
 (FRAG_ST_IPV4, FRAG_ST_FITS, FRAG_ST_DONE, FRAG_ST_DF, FRAG_ST_ISFRAG, FRAG_ST_BADCKSUM,
  FRAG_ST_NOROOM) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
+# struct pptk_tunnel and the status bits of pptk_tunnel_encap_* / _decap_*
+TUNNEL_DTYPE = np.dtype([("eth_dst", "u1", 6), ("eth_src", "u1", 6), ("src", "<u4"),
+                         ("dst", "<u4"), ("id", "<u2"), ("ttl", "u1"), ("tos", "u1"),
+                         ("flags", "<u4"), ("reserved", "<u4")])
+assert TUNNEL_DTYPE.itemsize == 32
+TUN_DF, TUN_ID_SEQ, TUN_HDR_LEN = 0x1, 0x2, 38
+(TUN_ST_DONE, TUN_ST_RUNT, TUN_ST_TOOBIG, TUN_ST_NOROOM, TUN_ST_NOFLOW,
+ TUN_ST_BADTUN) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+(DECAP_ST_IPV4, DECAP_ST_GRE, DECAP_ST_OK, DECAP_ST_ISFRAG, DECAP_ST_BADCKSUM, DECAP_ST_SHORT,
+ DECAP_ST_GREOPT, DECAP_ST_PTYPE) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
 
 REC32_DTYPE = np.dtype([
     ("flow_hash", "<u8"),

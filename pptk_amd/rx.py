@@ -180,7 +180,9 @@ EXPORTS = ("pptk_rx_opts_default", "pptk_rx_ctx_create", "pptk_rx_ctx_destroy",
            "pptk_tx_rewrite_device",
            "pptk_tcp_mss_clamp_device", "pptk_tcp_seq_translate_device",
            "pptk_tcp_seq_translate_hdr", "pptk_ip_fragment_scratch_bytes",
-           "pptk_ip_fragment_device", "pptk_ip_fragment_host", "pptk_rx_autotune", "pptk_rx_place_records",
+           "pptk_ip_fragment_device", "pptk_ip_fragment_host",
+           "pptk_tunnel_encap_device", "pptk_tunnel_decap_device",
+           "pptk_tunnel_encap_host", "pptk_tunnel_decap_host", "pptk_rx_autotune", "pptk_rx_place_records",
            "pptk_rx_place_buffers", "pptk_rx_ring_alloc", "pptk_rx_ring_free",
            "pptk_rx_gather_alloc", "pptk_rx_gather_free",
            # multi-GPU (RCCL)
@@ -298,6 +300,21 @@ def lib(path=None):
             L.pptk_ip_fragment_host.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp,
                                                 ctypes.c_uint64, ctypes.c_uint32, vp, vp]
             L.pptk_ip_fragment_host.restype = ctypes.c_int
+        if hasattr(L, "pptk_tunnel_encap_device"):     # absent from older A/B builds
+            L.pptk_tunnel_encap_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
+                                                   ctypes.c_uint32, ctypes.c_uint64, vp,
+                                                   ctypes.c_uint64, vp, ctypes.c_uint32, vp,
+                                                   ctypes.c_uint64, vp, vp, vp]
+            L.pptk_tunnel_encap_device.restype = ctypes.c_int
+            L.pptk_tunnel_decap_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
+                                                   ctypes.c_uint32, ctypes.c_uint64, vp, vp, vp,
+                                                   vp]
+            L.pptk_tunnel_decap_device.restype = ctypes.c_int
+            L.pptk_tunnel_encap_host.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp,
+                                                 ctypes.c_uint64, vp]
+            L.pptk_tunnel_encap_host.restype = ctypes.c_uint32
+            L.pptk_tunnel_decap_host.argtypes = [vp, ctypes.c_uint32, vp, vp]
+            L.pptk_tunnel_decap_host.restype = ctypes.c_uint32
         if hasattr(L, "pptk_rx_permit_device"):        # absent from older A/B builds
             L.pptk_rx_permit_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
             L.pptk_rx_permit_scratch_bytes.restype = ctypes.c_size_t
@@ -761,6 +778,74 @@ class RxContext:
         return dict(out=out, out_stride=out_stride, out_len=out_len, out_src=out_src, first=first,
                     count=count, status=status, totals=totals, scratch=scratch)
 
+    def tunnel_encap_device(self, frames, n, tun, idx=None, id_base=0, off=None, lens=None,
+                            stride=0, fixed_len=0, out=None, out_stride=0, out_len=None,
+                            status=None, stream=None):
+        """GRE encapsulation (pptk_tunnel_encap_device), asynchronous: slot i
+        = 38-byte outer header + frame i.  tun: struct pptk_tunnel entries
+        (records.TUNNEL_DTYPE) -- 1 or n of them, or a table indexed by idx
+        (torch int32 CUDA tensor of n entries, -1 = 0xffffffff = no tunnel)
+        -- as a NumPy array, which is checked (EINVAL for a non-zero
+        `reserved` or an unknown flag bit) and uploaded, or as a torch CUDA
+        tensor, which is passed as it is.  Allocates what is not given -- out
+        ((n, out_stride) uint8; out_stride = round_up(38 + fixed_len, 16)
+        unless given, and required with lens), out_len (int16), status (uint8) --
+        and returns them as a dict; out_len holds the C array's uint16 bits."""
+        import torch
+        from .records import TUN_DF, TUN_HDR_LEN, TUN_ID_SEQ, TUNNEL_DTYPE
+        if not hasattr(self._L, "pptk_tunnel_encap_device"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_tunnel_encap_device")
+        dev = frames.device
+        if isinstance(tun, np.ndarray):
+            t = np.ascontiguousarray(tun, dtype=TUNNEL_DTYPE).reshape(-1)
+            if np.any(t["reserved"]) or np.any(t["flags"] & ~np.uint32(TUN_DF | TUN_ID_SEQ)):
+                raise OSError(22, "struct pptk_tunnel: reserved must be 0, flags DF | ID_SEQ")
+            tun = torch.from_numpy(t.view(np.uint8).copy()).to(dev)
+        count = tun.numel() * tun.element_size() // 32
+        if not out_stride:
+            if lens is not None:   # (the lengths are device data: n x 64 KB would be the only safe guess)
+                raise ValueError("tunnel_encap_device: out_stride is required with lens")
+            out_stride = (TUN_HDR_LEN + fixed_len + 15) & ~15
+        if out is None:
+            out = torch.empty((n, out_stride), dtype=torch.uint8, device=dev)
+        if out_len is None:
+            out_len = torch.empty(n, dtype=torch.int16, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        rc = self._L.pptk_tunnel_encap_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
+                                              fixed_len, n, _dp(tun), count, _dp(idx), id_base,
+                                              _dp(out), out_stride, _dp(out_len), _dp(status),
+                                              ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_tunnel_encap_device failed ({rc})")
+        return dict(out=out, out_stride=out_stride, out_len=out_len, status=status, tun=tun)
+
+    def tunnel_decap_device(self, frames, n, off=None, lens=None, stride=0, fixed_len=0,
+                            in_off=None, in_len=None, status=None, stream=None):
+        """GRE decapsulation (pptk_tunnel_decap_device), asynchronous and
+        zero-copy: descriptors of the inner frames inside `frames`.
+        Allocates what is not given -- in_off (int64), in_len (int16), status
+        (uint8) -- and returns them as a dict; in_off / in_len go into
+        batch_device as off / lens."""
+        import torch
+        if not hasattr(self._L, "pptk_tunnel_decap_device"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_tunnel_decap_device")
+        dev = frames.device
+        if in_off is None:
+            in_off = torch.empty(n, dtype=torch.int64, device=dev)
+        if in_len is None:
+            in_len = torch.empty(n, dtype=torch.int16, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        rc = self._L.pptk_tunnel_decap_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
+                                              fixed_len, n, _dp(in_off), _dp(in_len), _dp(status),
+                                              ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_tunnel_decap_device failed ({rc})")
+        return dict(in_off=in_off, in_len=in_len, status=status)
+
     # ---- multi-GPU (RCCL) -------------------------------------------------
     def comm_create(self, nranks, rank, uid):
         """Join communicator `uid` (bytes from comm_uid()) as rank/nranks."""
@@ -913,6 +998,39 @@ def ip_fragment_host(frame, mtu, out_cap, out_stride=0, lib_path=None):
     if rc < 0:
         raise OSError(-rc, f"pptk_ip_fragment_host failed ({rc})")
     return rc, status.value, out[:out_cap], out_len[:out_cap]
+
+
+def tunnel_encap_host(frame, tun, seq=0, out_cap=None, lib_path=None):
+    """pptk_tunnel_encap_host on one frame (bytes) with one struct
+    pptk_tunnel (a records.TUNNEL_DTYPE entry or its 32 bytes): (status, out,
+    out_len) with out an out_cap-byte uint8 array (round_up(38 + len, 16)
+    unless given) pre-filled with 0xEE."""
+    L = lib(lib_path)
+    if not hasattr(L, "pptk_tunnel_encap_host"):
+        raise OSError(38, "this libpptkrx.so lacks pptk_tunnel_encap_host")
+    t = np.frombuffer(tun.tobytes() if hasattr(tun, "tobytes") else bytes(tun), np.uint8)
+    if t.size != 32:
+        raise ValueError("tun must be one struct pptk_tunnel (32 bytes)")
+    frame = bytes(frame)
+    if out_cap is None:
+        out_cap = (38 + len(frame) + 15) & ~15
+    out = np.full(max(out_cap, 1), 0xEE, np.uint8)
+    out_len = ctypes.c_uint16(0xEEEE)
+    st = L.pptk_tunnel_encap_host(frame, len(frame), t.ctypes.data, seq, out.ctypes.data, out_cap,
+                                  ctypes.byref(out_len))
+    return st, out[:out_cap], out_len.value
+
+
+def tunnel_decap_host(frame, lib_path=None):
+    """pptk_tunnel_decap_host on one frame (bytes): (status, in_off, in_len),
+    the inner frame being frame[in_off:in_off + in_len] when status has OK."""
+    L = lib(lib_path)
+    if not hasattr(L, "pptk_tunnel_decap_host"):
+        raise OSError(38, "this libpptkrx.so lacks pptk_tunnel_decap_host")
+    frame = bytes(frame)
+    in_off, in_len = ctypes.c_uint32(0xEEEEEEEE), ctypes.c_uint16(0xEEEE)
+    st = L.pptk_tunnel_decap_host(frame, len(frame), ctypes.byref(in_off), ctypes.byref(in_len))
+    return st, in_off.value, in_len.value
 
 
 def tcp_seq_translate_hdr(segment_bytes, xl, lib_path=None):
