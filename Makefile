@@ -13,11 +13,12 @@ CFLAGS := -O2 -std=gnu11 -fPIC -Wall -Wextra -Iinclude
 LIB := pptk_amd/libpptkrx.so
 HIP_SRCS := pptk_amd/csrc/rx_kernel.hip pptk_amd/csrc/rx_bin.hip pptk_amd/csrc/rx_permit.hip \
             pptk_amd/csrc/rx_capi.hip pptk_amd/csrc/rx_comm.hip pptk_amd/csrc/rx_ring.hip \
-            pptk_amd/csrc/tx_frag.hip pptk_amd/csrc/tx_tunnel.hip
+            pptk_amd/csrc/tx_frag.hip pptk_amd/csrc/tx_tunnel.hip pptk_amd/csrc/tx_hdr.hip
 C_SRCS := pptk_amd/csrc/host/ipcksum.c pptk_amd/csrc/host/hashseed.c pptk_amd/csrc/host/tcpopt.c \
           pptk_amd/csrc/host/iphash.c pptk_amd/csrc/host/timerlink.c pptk_amd/csrc/host/ipfrag.c \
           pptk_amd/csrc/host/tcpseq.c pptk_amd/csrc/host/tunnel.c
-HDRS := $(wildcard include/*.h) pptk_amd/csrc/rx_internal.h pptk_amd/csrc/copy16.h
+HDRS := $(wildcard include/*.h) pptk_amd/csrc/rx_internal.h pptk_amd/csrc/copy16.h \
+        pptk_amd/csrc/frame_view.h
 HIP_OBJS := $(patsubst pptk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
 C_OBJS := $(patsubst pptk_amd/csrc/host/%.c,$(OBJDIR)/host/%.o,$(C_SRCS))
 
@@ -62,9 +63,11 @@ abvariant:
 	$(MAKE) OBJDIR=build/ab_$(NAME)/obj LIB=build/ab_$(NAME)/libpptkrx.so \
 	  HIPFLAGS="$(HIPFLAGS) $(DEFS)" build/ab_$(NAME)/libpptkrx.so
 
+# the kernel files' assembly and resource tables (build/asm/<file>.resource.txt)
+ASM_SRCS := rx_kernel tx_hdr
 asm: $(HIP_SRCS)
 	@mkdir -p build/asm
-	cd build/asm && $(HIPCC) $(HIPFLAGS) -I../../include -c ../../pptk_amd/csrc/rx_kernel.hip -save-temps -o rx_kernel.o -Rpass-analysis=kernel-resource-usage 2> resource.txt; true
+	cd build/asm && for f in $(ASM_SRCS); do $(HIPCC) $(HIPFLAGS) -I../../include -c ../../pptk_amd/csrc/$$f.hip -save-temps -o $$f.o -Rpass-analysis=kernel-resource-usage 2> $$f.resource.txt; done; true
 
 clean:
 	rm -rf build $(LIB)

@@ -1,7 +1,9 @@
 // copy16.h -- the device helpers of the re-aligning 16-byte-chunk copies
 // (tx_frag.hip emit, tx_tunnel.hip encap) and of their header parses: the
 // source at any byte address, the destination chunk 16-byte aligned, and
-// nothing outside the aligned chunks of the source range is read.
+// nothing outside the aligned chunks of the source range is read.  The chunk
+// type and the 16-bit sum helpers also serve rx_kernel.hip and tx_hdr.hip,
+// through frame_view.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

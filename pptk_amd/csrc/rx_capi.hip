@@ -264,6 +264,26 @@ static uint64_t le64(const uint8_t *p) {
   return v;
 }
 
+// The part the in-place header ops share: the checks on the batch layout
+// (`op_ok` is the calling op's verdict on its own arguments), the context's
+// device, the batch descriptor and the grid (one lane per frame, at most
+// eight blocks per CU, grid-stride beyond).
+template <class Launch>
+static int hdr_op(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_t *d_off,
+                  const uint16_t *d_len, uint64_t stride, uint32_t fixed_len, uint64_t n,
+                  uint8_t *d_status, bool op_ok, Launch launch) {
+  if (!c || n > 0xffffffffull) return -EINVAL;
+  if (n == 0) return 0;
+  if (!d_frames || !op_ok || (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535))
+    return -EINVAL;
+  DeviceScope dg(c->device);
+  if (!dg.ok) return -EIO;
+  const HdrBatch b = {d_frames, d_frames, d_off, d_len, stride, n, fixed_len, d_status};
+  const uint64_t blocks = (n + 255) / 256;
+  const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)c->ncu * 8);
+  return hip_err(launch(b, grid));
+}
+
 extern "C" {
 
 const char *pptk_rx_version(void) { return "pptk_amd rx 0.6 gfx950"; }
@@ -893,83 +913,36 @@ int pptk_tx_rewrite_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint6
                            const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
                            uint64_t n, const struct pptk_rewrite *d_rw, uint64_t rw_count,
                            uint8_t *d_status, void *stream) {
-  if (!c || n > 0xffffffffull) return -EINVAL;
-  if (n == 0) return 0;
-  if (!d_frames || !d_rw || (rw_count != 1 && rw_count != n) ||
-      (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535))
-    return -EINVAL;
-  DeviceScope dg(c->device);
-  if (!dg.ok) return -EIO;
-  RxKArgs a = c->tmpl;
-  a.frames = d_frames;
-  a.frames_w = d_frames;
-  a.off = d_off;
-  a.len = d_len;
-  a.stride = stride;
-  a.fixed_len = fixed_len;
-  a.n = n;
-  a.rw = d_rw;
-  a.rw_one = rw_count == 1 ? 1u : 0u;
-  a.rw_status = d_status;
-  const uint64_t blocks = (n + 255) / 256;
-  const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)c->ncu * 8);
-  return hip_err(launch_rewrite(a, grid, (hipStream_t)stream));
+  const bool ok = d_rw && (rw_count == 1 || rw_count == n);
+  return hdr_op(c, d_frames, d_off, d_len, stride, fixed_len, n, d_status, ok,
+                [&](const HdrBatch &b, int grid) {
+                  const RewriteKArgs a = {b, d_rw, rw_count == 1 ? 1u : 0u};
+                  return launch_rewrite(a, grid, (hipStream_t)stream);
+                });
 }
 
 int pptk_tcp_mss_clamp_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_t *d_off,
                               const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
                               uint64_t n, uint16_t mss, uint32_t flags, uint8_t *d_status,
                               void *stream) {
-  if (!c || n > 0xffffffffull) return -EINVAL;
-  if (n == 0) return 0;
-  if (!d_frames || (flags & ~PPTK_MSS_SYN_ONLY) || (!d_off && stride == 0 && n > 1) ||
-      (!d_len && fixed_len > 65535))
-    return -EINVAL;
-  DeviceScope dg(c->device);
-  if (!dg.ok) return -EIO;
-  RxKArgs a = c->tmpl;
-  a.frames = d_frames;
-  a.frames_w = d_frames;
-  a.off = d_off;
-  a.len = d_len;
-  a.stride = stride;
-  a.fixed_len = fixed_len;
-  a.n = n;
-  a.mss = mss;
-  a.mss_flags = flags;
-  a.rw_status = d_status;
-  const uint64_t blocks = (n + 255) / 256;
-  const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)c->ncu * 8);
-  return hip_err(launch_mss_clamp(a, grid, (hipStream_t)stream));
+  const bool ok = !(flags & ~PPTK_MSS_SYN_ONLY);
+  return hdr_op(c, d_frames, d_off, d_len, stride, fixed_len, n, d_status, ok,
+                [&](const HdrBatch &b, int grid) {
+                  const MssKArgs a = {b, mss, flags};
+                  return launch_mss_clamp(a, grid, (hipStream_t)stream);
+                });
 }
 
 int pptk_tcp_seq_translate_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_t *d_off,
                                   const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
                                   uint64_t n, const struct pptk_seqxlate *d_xl, uint64_t xl_count,
                                   const uint32_t *d_idx, uint8_t *d_status, void *stream) {
-  if (!c || n > 0xffffffffull) return -EINVAL;
-  if (n == 0) return 0;
-  if (!d_frames || !d_xl || xl_count == 0 || (!d_idx && xl_count != 1 && xl_count != n) ||
-      (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535))
-    return -EINVAL;
-  DeviceScope dg(c->device);
-  if (!dg.ok) return -EIO;
-  SeqKArgs a;
-  a.frames = d_frames;
-  a.frames_w = d_frames;
-  a.off = d_off;
-  a.len = d_len;
-  a.stride = stride;
-  a.n = n;
-  a.xl = d_xl;
-  a.xl_count = xl_count;
-  a.idx = d_idx;
-  a.status = d_status;
-  a.fixed_len = fixed_len;
-  a.xl_one = !d_idx && xl_count == 1 ? 1u : 0u;
-  const uint64_t blocks = (n + 255) / 256;
-  const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)c->ncu * 8);
-  return hip_err(launch_seq_translate(a, grid, (hipStream_t)stream));
+  const bool ok = d_xl && xl_count != 0 && (d_idx || xl_count == 1 || xl_count == n);
+  return hdr_op(c, d_frames, d_off, d_len, stride, fixed_len, n, d_status, ok,
+                [&](const HdrBatch &b, int grid) {
+                  const SeqKArgs a = {b, d_xl, xl_count, d_idx, !d_idx && xl_count == 1 ? 1u : 0u};
+                  return launch_seq_translate(a, grid, (hipStream_t)stream);
+                });
 }
 
 // The length groups of the mixed path: kGroupMaxLen, or (A/B experiment)

@@ -88,13 +88,6 @@ struct RxKArgs {
   // 1: off/len are indexed by processing position (binned descriptors,
   // pptk_rx_batch_device_mixed), perm only gives the record index
   uint32_t by_pos;
-  // header rewrite (pptk_tx_rewrite_device): rw[rw_one ? 0 : i], status
-  const pptk_rewrite *rw;
-  uint32_t rw_one;
-  uint8_t *rw_status;
-  // MSS clamping (pptk_tcp_mss_clamp_device): new MSS, PPTK_MSS_* flags;
-  // the per-frame status goes to rw_status
-  uint32_t mss, mss_flags;
   // binned launches of pptk_rx_batch_device_mixed: the binning's plan word
   // (device; bit 0 = binned; else bits 8-15 = the group whose launch runs
   // the whole batch in batch order), the caller's own descriptors for that
@@ -167,26 +160,42 @@ bool rx_variant_phased(int variant);
 // fields txside[i] names; base(i) = off ? off[i] : i * stride
 hipError_t launch_tx_apply(const uint64_t *txside, uint8_t *frames, const uint64_t *off,
                            uint64_t stride, uint64_t n, hipStream_t s);
-hipError_t launch_rewrite(const RxKArgs &a, int grid, hipStream_t s);
-hipError_t launch_mss_clamp(const RxKArgs &a, int grid, hipStream_t s);
 
-// Arguments of the sequence-space translation kernel
-// (pptk_tcp_seq_translate_device): its own small struct, so that RxKArgs --
-// and with it the receive kernels' argument layout -- stays as it is.
-struct SeqKArgs {
+// The in-place header kernels (tx_hdr.hip) have small argument structs of
+// their own, so that RxKArgs -- and with it the receive kernels' argument
+// layout -- does not change with them.  All three work on a batch of frames
+// edited in place:
+struct HdrBatch {
   const uint8_t *frames;
-  uint8_t *frames_w;
+  uint8_t *frames_w;     // the same frames, writable
   const uint64_t *off;   // nullable -> fixed stride
   const uint16_t *len;   // nullable -> fixed_len
   uint64_t stride;
   uint64_t n;
+  uint32_t fixed_len;
+  uint8_t *status;       // nullable: per-frame status byte
+};
+// header rewrite (pptk_tx_rewrite_device): rw[rw_one ? 0 : i]
+struct RewriteKArgs {
+  HdrBatch b;
+  const pptk_rewrite *rw;
+  uint32_t rw_one;
+};
+// MSS clamping (pptk_tcp_mss_clamp_device): new MSS, PPTK_MSS_* flags
+struct MssKArgs {
+  HdrBatch b;
+  uint32_t mss, flags;
+};
+// sequence-space translation (pptk_tcp_seq_translate_device)
+struct SeqKArgs {
+  HdrBatch b;
   const pptk_seqxlate *xl;
   uint64_t xl_count;
   const uint32_t *idx;   // nullable -> xl[xl_one ? 0 : i]
-  uint8_t *status;       // nullable
-  uint32_t fixed_len;
   uint32_t xl_one;
 };
+hipError_t launch_rewrite(const RewriteKArgs &a, int grid, hipStream_t s);
+hipError_t launch_mss_clamp(const MssKArgs &a, int grid, hipStream_t s);
 hipError_t launch_seq_translate(const SeqKArgs &a, int grid, hipStream_t s);
 int rx_variant_blocks_per_cu(int variant);
 

@@ -16,13 +16,11 @@
 // workgroup.
 #include <errno.h>
 
-#include "copy16.h"
+#include "frame_view.h"
 #include "rx_internal.h"
 
 namespace pptk {
 namespace {
-
-#define LDS_AS __attribute__((address_space(3)))
 
 constexpr int kTile = 256;                  // frames per plan / apply block = scan tile
 constexpr int kScanThreads = 1024;
@@ -95,7 +93,7 @@ __device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
 
 // ---- plan ------------------------------------------------------------------
 // The subject test is the IPv4 branch of the receive transform's parse
-// (rx_kernel.hip parse_frame): one optional 802.1Q tag, ethertype 0x0800,
+// (frame_view.h parse_frame): one optional 802.1Q tag, ethertype 0x0800,
 // version 4, 20 <= ihl <= tl, l2 + tl <= len.  A frame shorter than 14 bytes
 // is not read at all; every other read lies inside the frame.
 __global__ __launch_bounds__(kTile) void frag_plan_kernel(FragArgs a) {

@@ -8,7 +8,7 @@ slots (SEQ | ACK | TSVAL | TSECHO, a spliced flow's every packet), and
 1500-byte segments with TS + SACK(2) in 1536-byte slots, all ops.
 
     python tools/ab_seq.py
-    AB_LIBS=bytes=build/ab_seqbytes/libpptkrx.so python tools/ab_seq.py
+    AB_LIBS=old=build/ab_old/libpptkrx.so python tools/ab_seq.py
     AB_FRAMES=... AB_ROUNDS=... AB_STEPS=...
 """
 import json
