@@ -13,12 +13,13 @@ CFLAGS := -O2 -std=gnu11 -fPIC -Wall -Wextra -Iinclude
 LIB := pptk_amd/libpptkrx.so
 HIP_SRCS := pptk_amd/csrc/rx_kernel.hip pptk_amd/csrc/rx_bin.hip pptk_amd/csrc/rx_permit.hip \
             pptk_amd/csrc/rx_capi.hip pptk_amd/csrc/rx_comm.hip pptk_amd/csrc/rx_ring.hip \
-            pptk_amd/csrc/tx_frag.hip pptk_amd/csrc/tx_tunnel.hip pptk_amd/csrc/tx_hdr.hip
+            pptk_amd/csrc/tx_frag.hip pptk_amd/csrc/tx_tunnel.hip pptk_amd/csrc/tx_hdr.hip \
+            pptk_amd/csrc/rx_flow.hip
 C_SRCS := pptk_amd/csrc/host/ipcksum.c pptk_amd/csrc/host/hashseed.c pptk_amd/csrc/host/tcpopt.c \
           pptk_amd/csrc/host/iphash.c pptk_amd/csrc/host/timerlink.c pptk_amd/csrc/host/ipfrag.c \
-          pptk_amd/csrc/host/tcpseq.c pptk_amd/csrc/host/tunnel.c
+          pptk_amd/csrc/host/tcpseq.c pptk_amd/csrc/host/tunnel.c pptk_amd/csrc/host/flowtab.c
 HDRS := $(wildcard include/*.h) pptk_amd/csrc/rx_internal.h pptk_amd/csrc/copy16.h \
-        pptk_amd/csrc/frame_view.h
+        pptk_amd/csrc/frame_view.h pptk_amd/csrc/flowtab.h
 HIP_OBJS := $(patsubst pptk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
 C_OBJS := $(patsubst pptk_amd/csrc/host/%.c,$(OBJDIR)/host/%.o,$(C_SRCS))
 
@@ -59,6 +60,7 @@ all: $(HOOKS_LIB)
 
 # A/B builds of the product library with extra defines, e.g.
 #   make abvariant NAME=full DEFS=-DPPTK_RX_FULL_UNROLL
+#   make abvariant NAME=flow4 DEFS=-DPPTK_FLOW_TEAM=4   (rx_flow.hip: four lanes per record)
 abvariant:
 	$(MAKE) OBJDIR=build/ab_$(NAME)/obj LIB=build/ab_$(NAME)/libpptkrx.so \
 	  HIPFLAGS="$(HIPFLAGS) $(DEFS)" build/ab_$(NAME)/libpptkrx.so

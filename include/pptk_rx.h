@@ -442,7 +442,7 @@ int pptk_tcp_mss_clamp_device(struct pptk_rx_ctx *ctx, uint8_t *d_frames, const 
  * iphdr/ipcksum.h:395-623 and iphdr/iphdr.c:134-246.  Frame i takes the
  * translation d_xl[0] or d_xl[i] (d_idx NULL: xl_count must be 1 or n, as
  * pptk_tx_rewrite_device) or d_xl[d_idx[i]] (the result of a flow-table
- * lookup); an index >= xl_count (use 0xffffffff) means "no flow": the frame
+ * lookup, pptk_flow_lookup_device below); an index >= xl_count (use 0xffffffff) means "no flow": the frame
  * is neither read nor written and its status is PPTK_SEQ_ST_NOFLOW.
  * Subjects are the frames whose receive record would be PPTK_RX_F_PARSED,
  * not MALFORMED, PPTK_RX_F_L4 and proto 6 (IPv4 or IPv6, with or without a
@@ -721,6 +721,117 @@ uint32_t pptk_tunnel_encap_host(const void *frame, uint32_t len, const struct pp
                                 uint16_t *out_len);
 uint32_t pptk_tunnel_decap_host(const void *frame, uint32_t len, uint32_t *in_off,
                                 uint16_t *in_len);
+
+/* Flow table: the step between the receive transform and the per-flow
+ * header edits.  pptk_tcp_seq_translate_device and pptk_tunnel_encap_device
+ * take a d_idx, "the flow of frame i"; this is what produces it:
+ *   rx -> pptk_flow_lookup_device -> seq-translate / rewrite / encap -> fragment
+ * all on batches that stay in device memory.  The structure is the
+ * reference's hashtable/hashtable.h: a power-of-two array addressed by
+ * bucket = hashval & (bucketcnt - 1) with hashval the SipHash of the key
+ * truncated to 32 bits, candidates compared key by key, never growing
+ * (hash_table_add_nogrow).  The table is managed on the host -- it is the
+ * control plane, as the reference's is -- and mirrored in device memory; one
+ * kernel turns a batch of records into d_idx.
+ *
+ * Shape.  `slots` is a power of two, 16 .. 2^26 (-EINVAL otherwise); the
+ * table holds at most slots / 2 flows and never grows (insert beyond:
+ * -ENOSPC).  ctx == NULL gives a host-only table: find and lookup_host work
+ * on it, sync and lookup_device return -EINVAL.  One writer at a time, no
+ * locking, as the reference's table.
+ *
+ * Hashing.  The table never hashes: the caller passes the flow_hash the
+ * receive transform wrote into the record, or, for a flow no frame of which
+ * it has seen yet, pptk_flow_key_hash(opts.key, &key): siphash_buf over
+ * src | dst | be16 sport | be16 dport | proto | 0 0 0, the 40 bytes the
+ * receive transform hashes, so that for every parsed frame it equals
+ * rec.flow_hash.  pptk_flow_key_from_rec copies a record's tuple into a key.
+ * A key whose zero[] is not 0 is -EINVAL everywhere.
+ *
+ * Probing.  The home slot is (uint32_t)flow_hash & (slots - 1), the
+ * reference's bucket; collisions resolve by linear probing with wrap-around.
+ * A slot matches when it is in use, its stored 64-bit hash equals the hash
+ * given and all 37 key bytes (src, dst, sport, dport, proto) are equal: a
+ * 64-bit hash match alone is never a hit.
+ *
+ * insert   0; -EEXIST for a key that is present (its value is left alone);
+ *          -ENOSPC at slots / 2 flows; -EINVAL for value PPTK_FLOW_NONE.
+ * update   sets the value of a present key; -ENOENT if absent.
+ * delete   backward-shift deletion: the image never holds tombstones and an
+ *          empty slot always ends a probe; -ENOENT if absent.
+ * find     0 and *value (nullable), or -ENOENT.
+ * insert_recs  inserts the key of every record that is a subject (below,
+ *          with d_subject NULL) with values[i]; results[i] (nullable) = 0,
+ *          -EEXIST, -ENOSPC, or -EINVAL for a non-subject or a bad value.
+ *          Returns the number inserted, or -EINVAL for null arguments.
+ * clear    empties the table.
+ * stats    slots, count and probe_limit (each nullable): probe_limit is 0 for
+ *          an empty table that has held nothing since the last clear, else
+ *          1 + the largest displacement from its home slot any entry has had
+ *          since then; it may stay high after deletes.
+ *
+ * sync uploads the slots that changed since the last sync, tracked at a
+ * granularity of 4 KB of image (a first sync uploads everything), on
+ * `stream`, and waits for the upload: on return the device image equals the
+ * host image.  *uploaded_bytes (nullable) is what it copied.  Device lookups
+ * see the table as of the last sync; ordering a sync against lookups in
+ * flight on other streams is the caller's duty.
+ *
+ * lookup.  A record is a subject when it has PPTK_RX_F_PARSED, lacks
+ * PPTK_RX_F_MALFORMED and d_subject[i] != 0 (or d_subject is NULL).  Its key
+ * is record bytes 8..43 plus proto, its hash flow_hash.  A subject found gets
+ * d_idx[i] = value and status SUBJECT | HIT; one not found PPTK_FLOW_NONE and
+ * SUBJECT; a non-subject PPTK_FLOW_NONE and 0.  PPTK_FLOW_NONE is the "no
+ * flow" index of pptk_tcp_seq_translate_device and pptk_tunnel_encap_device.
+ * Nothing is written past entry n - 1; n = 0 launches nothing.  The probe of
+ * a record ends at the first unused slot and after probe_limit slots at the
+ * latest (a kernel argument from the host's bookkeeping, never above
+ * `slots`), whatever the image holds.  d_recs must be 16-byte and d_idx 4-byte
+ * aligned; -EINVAL for that, for a null ctx, t, d_recs or d_idx (with n > 0),
+ * a host-only table, a table of another context's device or one never
+ * synced.  d_status is nullable.  Asynchronous on `stream`.
+ * pptk_flow_lookup_host is the same rule over the host image (idx required,
+ * subject and status nullable) and the CPU statement of this contract.
+ *
+ * Out of scope: inserts or deletes performed by a kernel, growth, idle expiry
+ * or last-seen stamps, per-flow counters, a direction-symmetric key (the
+ * caller inserts both directions), pptk_rx_rec32 input (it lacks the IPv6
+ * addresses), and locking. */
+struct pptk_flow_key {            /* 40 bytes: the tuple the flow hash covers */
+  uint8_t src[16], dst[16];       /* as pptk_rx_rec.src / .dst                */
+  uint16_t sport, dport;          /* host order, as the record                */
+  uint8_t proto;                  /* pptk_rx_rec.proto                        */
+  uint8_t zero[3];                /* must be 0 (-EINVAL otherwise)            */
+};
+#define PPTK_FLOW_NONE 0xffffffffu  /* d_idx value "no flow"; not a legal value to insert */
+#define PPTK_FLOW_ST_SUBJECT 0x1u
+#define PPTK_FLOW_ST_HIT     0x2u
+
+struct pptk_flow_table;
+int pptk_flow_table_create(struct pptk_rx_ctx *ctx, uint32_t slots, struct pptk_flow_table **t);
+void pptk_flow_table_destroy(struct pptk_flow_table *t);
+void pptk_flow_key_from_rec(const struct pptk_rx_rec *rec, struct pptk_flow_key *key);
+uint64_t pptk_flow_key_hash(const uint8_t key16[16], const struct pptk_flow_key *key);
+int pptk_flow_table_insert(struct pptk_flow_table *t, const struct pptk_flow_key *key,
+                           uint64_t flow_hash, uint32_t value);
+int pptk_flow_table_update(struct pptk_flow_table *t, const struct pptk_flow_key *key,
+                           uint64_t flow_hash, uint32_t value);
+int pptk_flow_table_delete(struct pptk_flow_table *t, const struct pptk_flow_key *key,
+                           uint64_t flow_hash);
+int pptk_flow_table_find(const struct pptk_flow_table *t, const struct pptk_flow_key *key,
+                         uint64_t flow_hash, uint32_t *value);
+int pptk_flow_table_insert_recs(struct pptk_flow_table *t, const struct pptk_rx_rec *recs,
+                                uint64_t n, const uint32_t *values, int32_t *results);
+void pptk_flow_table_clear(struct pptk_flow_table *t);
+void pptk_flow_table_stats(const struct pptk_flow_table *t, uint32_t *slots, uint32_t *count,
+                           uint32_t *probe_limit);
+int pptk_flow_table_sync(struct pptk_flow_table *t, void *stream, uint64_t *uploaded_bytes);
+int pptk_flow_lookup_device(struct pptk_rx_ctx *ctx, const struct pptk_flow_table *t,
+                            const struct pptk_rx_rec *d_recs, uint64_t n,
+                            const uint8_t *d_subject, uint32_t *d_idx, uint8_t *d_status,
+                            void *stream);
+int pptk_flow_lookup_host(const struct pptk_flow_table *t, const struct pptk_rx_rec *recs,
+                          uint64_t n, const uint8_t *subject, uint32_t *idx, uint8_t *status);
 
 /* Tuning: force kernel variant `variant` (0 .. pptk_rx_variant_count()-1)
  * and/or memory-policy flags for every later batch of this context; -1

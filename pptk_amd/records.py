@@ -55,6 +55,13 @@ TUN_DF, TUN_ID_SEQ, TUN_HDR_LEN = 0x1, 0x2, 38
  TUN_ST_BADTUN) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
 (DECAP_ST_IPV4, DECAP_ST_GRE, DECAP_ST_OK, DECAP_ST_ISFRAG, DECAP_ST_BADCKSUM, DECAP_ST_SHORT,
  DECAP_ST_GREOPT, DECAP_ST_PTYPE) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
+# struct pptk_flow_key (the flow table's key: the tuple the flow hash covers),
+# the "no flow" index and the status bits of pptk_flow_lookup_device / _host
+FLOW_KEY_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16), ("sport", "<u2"),
+                           ("dport", "<u2"), ("proto", "u1"), ("zero", "u1", 3)])
+assert FLOW_KEY_DTYPE.itemsize == 40
+FLOW_NONE = 0xFFFFFFFF
+FLOW_ST_SUBJECT, FLOW_ST_HIT = 0x1, 0x2
 
 REC32_DTYPE = np.dtype([
     ("flow_hash", "<u8"),

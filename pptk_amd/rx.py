@@ -182,7 +182,13 @@ EXPORTS = ("pptk_rx_opts_default", "pptk_rx_ctx_create", "pptk_rx_ctx_destroy",
            "pptk_tcp_seq_translate_hdr", "pptk_ip_fragment_scratch_bytes",
            "pptk_ip_fragment_device", "pptk_ip_fragment_host",
            "pptk_tunnel_encap_device", "pptk_tunnel_decap_device",
-           "pptk_tunnel_encap_host", "pptk_tunnel_decap_host", "pptk_rx_autotune", "pptk_rx_place_records",
+           "pptk_tunnel_encap_host", "pptk_tunnel_decap_host",
+           "pptk_flow_table_create", "pptk_flow_table_destroy", "pptk_flow_key_from_rec",
+           "pptk_flow_key_hash", "pptk_flow_table_insert", "pptk_flow_table_update",
+           "pptk_flow_table_delete", "pptk_flow_table_find", "pptk_flow_table_insert_recs",
+           "pptk_flow_table_clear", "pptk_flow_table_stats", "pptk_flow_table_sync",
+           "pptk_flow_lookup_device", "pptk_flow_lookup_host",
+           "pptk_rx_autotune", "pptk_rx_place_records",
            "pptk_rx_place_buffers", "pptk_rx_ring_alloc", "pptk_rx_ring_free",
            "pptk_rx_gather_alloc", "pptk_rx_gather_free",
            # multi-GPU (RCCL)
@@ -315,6 +321,35 @@ def lib(path=None):
             L.pptk_tunnel_encap_host.restype = ctypes.c_uint32
             L.pptk_tunnel_decap_host.argtypes = [vp, ctypes.c_uint32, vp, vp]
             L.pptk_tunnel_decap_host.restype = ctypes.c_uint32
+        if hasattr(L, "pptk_flow_table_create"):       # absent from older A/B builds
+            u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+            L.pptk_flow_table_create.argtypes = [vp, u32, ctypes.POINTER(vp)]
+            L.pptk_flow_table_create.restype = ctypes.c_int
+            L.pptk_flow_table_destroy.argtypes = [vp]
+            L.pptk_flow_table_destroy.restype = None
+            L.pptk_flow_key_from_rec.argtypes = [vp, vp]
+            L.pptk_flow_key_from_rec.restype = None
+            L.pptk_flow_key_hash.argtypes = [vp, vp]
+            L.pptk_flow_key_hash.restype = u64
+            for f in ("pptk_flow_table_insert", "pptk_flow_table_update"):
+                getattr(L, f).argtypes = [vp, vp, u64, u32]
+                getattr(L, f).restype = ctypes.c_int
+            L.pptk_flow_table_delete.argtypes = [vp, vp, u64]
+            L.pptk_flow_table_delete.restype = ctypes.c_int
+            L.pptk_flow_table_find.argtypes = [vp, vp, u64, ctypes.POINTER(u32)]
+            L.pptk_flow_table_find.restype = ctypes.c_int
+            L.pptk_flow_table_insert_recs.argtypes = [vp, vp, u64, vp, vp]
+            L.pptk_flow_table_insert_recs.restype = ctypes.c_int
+            L.pptk_flow_table_clear.argtypes = [vp]
+            L.pptk_flow_table_clear.restype = None
+            L.pptk_flow_table_stats.argtypes = [vp] + [ctypes.POINTER(u32)] * 3
+            L.pptk_flow_table_stats.restype = None
+            L.pptk_flow_table_sync.argtypes = [vp, vp, ctypes.POINTER(u64)]
+            L.pptk_flow_table_sync.restype = ctypes.c_int
+            L.pptk_flow_lookup_device.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
+            L.pptk_flow_lookup_device.restype = ctypes.c_int
+            L.pptk_flow_lookup_host.argtypes = [vp, vp, u64, vp, vp, vp]
+            L.pptk_flow_lookup_host.restype = ctypes.c_int
         if hasattr(L, "pptk_rx_permit_device"):        # absent from older A/B builds
             L.pptk_rx_permit_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
             L.pptk_rx_permit_scratch_bytes.restype = ctypes.c_size_t
@@ -846,6 +881,35 @@ class RxContext:
             raise OSError(-rc, f"pptk_tunnel_decap_device failed ({rc})")
         return dict(in_off=in_off, in_len=in_len, status=status)
 
+    def flow_table(self, slots):
+        """A flow table of `slots` slots mirrored on this context's device."""
+        return FlowTable(slots, ctx=self)
+
+    def flow_lookup_device(self, table, recs, subject=None, idx=None, status=None, stream=None):
+        """pptk_flow_lookup_device, asynchronous: recs is the uint8 CUDA
+        tensor of n 64-byte records batch_device returned, table a synced
+        FlowTable of this context; subject: optional uint8 CUDA tensor of n
+        entries.  Allocates what is not given and returns (idx, status): idx
+        int32 (the C array's uint32 bits, -1 = FLOW_NONE = no flow), ready to
+        be the idx= of seq_translate_device / tunnel_encap_device; status
+        uint8 FLOW_ST_* bits."""
+        import torch
+        if not hasattr(self._L, "pptk_flow_lookup_device"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_flow_lookup_device")
+        dev = recs.device
+        n = recs.numel() * recs.element_size() // 64
+        if idx is None:
+            idx = torch.empty(n, dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        rc = self._L.pptk_flow_lookup_device(self._ctx, table._t, _dp(recs), n, _dp(subject),
+                                             _dp(idx), _dp(status),
+                                             ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_lookup_device failed ({rc})")
+        return idx, status
+
     # ---- multi-GPU (RCCL) -------------------------------------------------
     def comm_create(self, nranks, rank, uid):
         """Join communicator `uid` (bytes from comm_uid()) as rank/nranks."""
@@ -982,6 +1046,164 @@ class RxContext:
 
     def pending_host(self):
         return self._L.pptk_rx_batch_pending(self._ctx)
+
+
+def _flow_key(key):
+    """One struct pptk_flow_key as a 40-byte uint8 array, from a
+    records.FLOW_KEY_DTYPE entry or its bytes."""
+    k = np.frombuffer(key.tobytes() if hasattr(key, "tobytes") else bytes(key), np.uint8)
+    if k.size != 40:
+        raise ValueError("key must be one struct pptk_flow_key (40 bytes)")
+    return k
+
+
+def flow_key_hash(key16, key, lib_path=None):
+    """pptk_flow_key_hash: the flow hash the receive transform gives the
+    tuple `key` (a records.FLOW_KEY_DTYPE entry) under the SipHash key."""
+    key16 = bytes(key16)
+    if len(key16) != 16:
+        raise ValueError("key16 must be 16 bytes")
+    k = _flow_key(key)   # (kept alive across the call)
+    return lib(lib_path).pptk_flow_key_hash(key16, k.ctypes.data)
+
+
+def flow_key_from_rec(rec, lib_path=None):
+    """pptk_flow_key_from_rec: the records.FLOW_KEY_DTYPE entry of one record
+    (a records.REC_DTYPE entry or its 64 bytes)."""
+    from .records import FLOW_KEY_DTYPE
+    r = np.frombuffer(rec.tobytes() if hasattr(rec, "tobytes") else bytes(rec), np.uint8)
+    if r.size != 64:
+        raise ValueError("rec must be one struct pptk_rx_rec (64 bytes)")
+    k = np.full(1, 0xEE, np.uint8).repeat(40)
+    lib(lib_path).pptk_flow_key_from_rec(r.ctypes.data, k.ctypes.data)
+    return k.view(FLOW_KEY_DTYPE)[0]
+
+
+class FlowTable:
+    """One pptk_flow_table: FlowTable(slots) is host-only, RxContext.flow_table
+    (slots) is mirrored on the context's device (sync, flow_lookup_device).
+    Keys are records.FLOW_KEY_DTYPE entries (or their 40 bytes); the errno
+    returns of the C calls are raised as OSError, except where a method's
+    docstring says it returns them."""
+
+    def __init__(self, slots, ctx=None, lib_path=None):
+        self._L = L = ctx._L if ctx is not None else lib(lib_path)
+        if not hasattr(L, "pptk_flow_table_create"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_flow_table_create")
+        self._t = ctypes.c_void_p()
+        self._ctx = ctx   # (keeps the context alive as long as the table)
+        rc = L.pptk_flow_table_create(ctx._ctx if ctx is not None else None, slots,
+                                      ctypes.byref(self._t))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_table_create({slots}) failed ({rc})")
+
+    def close(self):
+        if self._t:
+            self._L.pptk_flow_table_destroy(self._t)
+            self._t = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def insert_rc(self, key, flow_hash, value):
+        """pptk_flow_table_insert's return code (0, -EEXIST, -ENOSPC, -EINVAL)."""
+        k = _flow_key(key)   # (kept alive across the call)
+        return self._L.pptk_flow_table_insert(self._t, k.ctypes.data, flow_hash, value)
+
+    def update_rc(self, key, flow_hash, value):
+        k = _flow_key(key)
+        return self._L.pptk_flow_table_update(self._t, k.ctypes.data, flow_hash, value)
+
+    def delete_rc(self, key, flow_hash):
+        k = _flow_key(key)
+        return self._L.pptk_flow_table_delete(self._t, k.ctypes.data, flow_hash)
+
+    def insert(self, key, flow_hash, value):
+        rc = self.insert_rc(key, flow_hash, value)
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_table_insert failed ({rc})")
+
+    def update(self, key, flow_hash, value):
+        rc = self.update_rc(key, flow_hash, value)
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_table_update failed ({rc})")
+
+    def delete(self, key, flow_hash):
+        rc = self.delete_rc(key, flow_hash)
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_table_delete failed ({rc})")
+
+    def find(self, key, flow_hash):
+        """The key's value, or None if it is absent."""
+        v = ctypes.c_uint32(0)
+        k = _flow_key(key)
+        rc = self._L.pptk_flow_table_find(self._t, k.ctypes.data, flow_hash, ctypes.byref(v))
+        if rc == -2:
+            return None
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_table_find failed ({rc})")
+        return v.value
+
+    def insert_recs(self, recs, values):
+        """pptk_flow_table_insert_recs over a NumPy array of records
+        (records.REC_DTYPE, or its bytes): (number inserted, int32 results)."""
+        r = np.ascontiguousarray(recs).view(np.uint8).reshape(-1)
+        n = r.size // 64
+        v = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+        if r.size != n * 64 or v.size != n:
+            raise ValueError("insert_recs: n 64-byte records and n values")
+        res = np.zeros(max(n, 1), np.int32)
+        rc = self._L.pptk_flow_table_insert_recs(self._t, r.ctypes.data, n, v.ctypes.data,
+                                                 res.ctypes.data)
+        if rc < 0:
+            raise OSError(-rc, f"pptk_flow_table_insert_recs failed ({rc})")
+        return rc, res[:n]
+
+    def clear(self):
+        self._L.pptk_flow_table_clear(self._t)
+
+    def stats(self):
+        """dict(slots, count, probe_limit)."""
+        a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._L.pptk_flow_table_stats(self._t, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+        return dict(slots=a.value, count=b.value, probe_limit=c.value)
+
+    def sync(self, stream=None):
+        """pptk_flow_table_sync on `stream` (torch stream or None = current):
+        the bytes it uploaded."""
+        if self._ctx is None:
+            s = None
+        else:
+            import torch
+            s = stream if stream is not None else torch.cuda.current_stream(self._ctx.device)
+            s = ctypes.c_void_p(s.cuda_stream)
+        up = ctypes.c_uint64(0)
+        rc = self._L.pptk_flow_table_sync(self._t, s, ctypes.byref(up))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_table_sync failed ({rc})")
+        return up.value
+
+    def lookup_host(self, recs, subject=None):
+        """pptk_flow_lookup_host over a NumPy array of records: (idx uint32,
+        status uint8)."""
+        r = np.ascontiguousarray(recs).view(np.uint8).reshape(-1)
+        n = r.size // 64
+        idx = np.zeros(max(n, 1), np.uint32)
+        st = np.zeros(max(n, 1), np.uint8)
+        sub = None
+        if subject is not None:
+            sub = np.ascontiguousarray(subject, dtype=np.uint8).reshape(-1)
+            if sub.size != n:
+                raise ValueError("lookup_host: one subject byte per record")
+        rc = self._L.pptk_flow_lookup_host(self._t, r.ctypes.data, n,
+                                           None if sub is None else sub.ctypes.data,
+                                           idx.ctypes.data, st.ctypes.data)
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_lookup_host failed ({rc})")
+        return idx[:n], st[:n]
 
 
 def ip_fragment_host(frame, mtu, out_cap, out_stride=0, lib_path=None):
