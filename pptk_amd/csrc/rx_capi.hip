@@ -1,25 +1,19 @@
 // rx_capi.hip -- the C-ABI shim of libpptkrx.so (include/pptk_rx.h).
 //
-// Host side of the drop-in: a context per rx thread (own stream, own pinned
-// staging), the device-resident batch entry point, the host-buffer batch
-// entry point that an LDP rx loop calls between ldp_in_nextpkts() and
-// ldp_in_deallocate_some() (reference ldp/ldprecv.c:60-70), and the
-// length-binning helper.  Error convention: 0 or -errno, never abort on
-// packet content.
+// The context (one per rx thread) and the device-batch API: the device-
+// resident batch entry points with their choice of variant, grid and memory
+// policy, autotune, the tx and header ops, the rate limiter, length binning
+// and the stream split.  The host-buffer batch pipeline, whose state the
+// context owns, is rx_host.hip.  Error convention: 0 or -errno, never abort
+// on packet content.
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <emmintrin.h>
-
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
-#include <memory>
-#include <functional>
 #include <mutex>
 #include <new>
-#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -28,139 +22,6 @@
 #include "rx_internal.h"
 
 using namespace pptk;
-
-// One part of a host chunk's descriptors (pptk_rx_batch): the staging bytes
-// its frames take and where they start, a ring chunk's span and frame bytes,
-// the longest frame.
-struct PartDesc {
-  size_t bytes = 0, base = 0;
-  size_t lo = SIZE_MAX, hi = 0, fbytes = 0;
-  uint32_t maxlen = 0;
-  // uniform frames: every frame of the part sz0 bytes (same), and at
-  // p0 + k * stride (uni; k = its index in the part); each cleared at the
-  // first frame that is not.  A staged chunk needs only `same` (the staging
-  // puts equal frames at one stride), a ring chunk both.
-  bool same = true, uni = true;
-  uint32_t sz0 = 0;
-  const uint8_t *p0 = nullptr;
-  int64_t stride = 0;
-  bool outside = false;   // a frame not (wholly) inside the candidate ring
-};
-
-// One half of the host-batch double buffer: pinned staging, device copies,
-// and the chunk currently in flight on its stream.
-struct RxSlot {
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;
-  size_t cap_pkts = 0, cap_bytes = 0;
-  size_t dev_cap = 0;   // d_frames bytes (grown for registered-ring spans)
-  uint8_t *h_frames = nullptr, *d_frames = nullptr;
-  uint64_t *h_off = nullptr, *d_off = nullptr;
-  uint16_t *h_len = nullptr, *d_len = nullptr;
-  pptk_rx_rec *h_recs = nullptr, *d_recs = nullptr;
-  // device addresses of the pinned h_* buffers (direct small chunks)
-  uint8_t *hd_frames = nullptr;
-  uint64_t *hd_off = nullptr;
-  uint16_t *hd_len = nullptr;
-  pptk_rx_rec *hd_recs = nullptr;
-  void *out = nullptr;   // caller's records of the chunk in flight
-  size_t count = 0;
-  size_t rec_bytes = 64;   // of the chunk in flight: 64 (pptk_rx_rec) or 32 (pptk_rx_rec32)
-  bool busy = false;
-  std::vector<PartDesc> parts;  // pptk_rx_batch's per-part descriptor sums
-  std::unique_ptr<std::atomic<size_t>[]> run;   // the parts' running staging totals
-  size_t run_cap = 0;
-};
-
-// The context's host worker threads (opts.gather_threads - 1 of them, started
-// on the first host batch and kept): parallel_for(n, f) runs f(0..n-1)
-// across them and the calling thread and returns when all are done.  The
-// staged path's frame gather and record copy-out use it; starting threads
-// per chunk instead cost more than the copies for small frames.
-class WorkerPool {
- public:
-  explicit WorkerPool(size_t nworkers) {
-    try {
-      for (size_t t = 0; t < nworkers; ++t) th_.emplace_back([this] { loop(); });
-    } catch (...) {   // a thread could not be started: stop the others
-      shutdown();
-      throw;
-    }
-  }
-  ~WorkerPool() { shutdown(); }
-  size_t size() const { return th_.size() + 1; }
-  void parallel_for(size_t n, const std::function<void(size_t)> &f) {
-    if (n == 0) return;
-    uint64_t gen;
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      job_ = &f;
-      n_ = n;
-      next_ = 0;
-      left_ = n;
-      gen = ++gen_;
-    }
-    cv_.notify_all();
-    work(gen);
-    std::unique_lock<std::mutex> g(mu_);
-    done_cv_.wait(g, [this] { return left_ == 0; });
-    job_ = nullptr;
-  }
-
- private:
-  // Items are claimed under the mutex together with the job they belong to:
-  // a worker still finishing generation k can never claim an index of
-  // generation k + 1 (which starts only after every item of k completed) or
-  // run one with a stale job pointer.  Items are ~256 frames or 1 MiB of
-  // copying, so a lock per claim costs nothing measurable.
-  void work(uint64_t gen) {
-    std::unique_lock<std::mutex> g(mu_);
-    for (;;) {
-      if (gen_ != gen || next_ >= n_) return;
-      const size_t i = next_++;
-      const std::function<void(size_t)> *job = job_;
-      g.unlock();
-      (*job)(i);
-      g.lock();
-      if (--left_ == 0) done_cv_.notify_all();
-    }
-  }
-  void loop() {
-    uint64_t seen = 0;
-    for (;;) {
-      {
-        std::unique_lock<std::mutex> g(mu_);
-        cv_.wait(g, [&] { return stop_ || gen_ != seen; });
-        if (stop_) return;
-        seen = gen_;
-      }
-      work(seen);
-    }
-  }
-  void shutdown() {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (std::thread &t : th_) t.join();
-    th_.clear();
-  }
-  std::vector<std::thread> th_;
-  std::mutex mu_;
-  std::condition_variable cv_, done_cv_;
-  const std::function<void(size_t)> *job_ = nullptr;
-  size_t n_ = 0, left_ = 0, next_ = 0;
-  uint64_t gen_ = 0;
-  bool stop_ = false;
-};
-
-// A host rx ring registered for zero-copy reads (hipHostRegister, mapped).
-struct RxRing {
-  uint8_t *host;
-  size_t bytes;
-  const uint8_t *dev;
-};
 
 struct pptk_rx_ctx {
   int device = 0;
@@ -190,13 +51,7 @@ struct pptk_rx_ctx {
   // pptk_rx_autotune's choice per automatic variant, for fixed-stride [0]
   // and offset-described [1] batches (-1: the automatic variant itself)
   int tuned[2][RX_NVARIANTS];
-  // host-batch pipeline: pptk_rx_batch double-buffers over slots 0 and 1,
-  // pptk_rx_batch_submit rotates over all of them (allocated on first use)
-  RxSlot slot[PPTK_RX_MAX_INFLIGHT];
-  int async_head = 0;  // slot of the oldest outstanding submission
-  int async_n = 0;     // outstanding submissions (0..PPTK_RX_MAX_INFLIGHT)
-  std::vector<RxRing> rings;
-  WorkerPool *pool = nullptr;   // started by the first host batch
+  HostPipe *host = nullptr;   // the host-batch pipeline's state (rx_host.hip)
   // RCCL communicator (rx_comm.hip), or null; atomic: pptk_rx_comm_abort
   // may read it from another rx thread while this one creates it
   std::atomic<void *> comm{nullptr};
@@ -204,6 +59,8 @@ struct pptk_rx_ctx {
 
 namespace pptk {
 int ctx_device(const pptk_rx_ctx *c) { return c->device; }
+const pptk_rx_opts &ctx_opts(const pptk_rx_ctx *c) { return c->opts; }
+HostPipe *ctx_host_pipe(const pptk_rx_ctx *c) { return c->host; }
 std::atomic<void *> *ctx_comm_slot(pptk_rx_ctx *c) { return &c->comm; }
 uint32_t ctx_comm_timeout_ms(const pptk_rx_ctx *c) {
   return c->opts.comm_timeout_ms ? c->opts.comm_timeout_ms : PPTK_RX_COMM_TIMEOUT_MS;
@@ -241,22 +98,6 @@ static void drop_split_streams(pptk_rx_ctx *c) {
 }
 
 static int hip_err(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
-// An integer environment knob, read once (the callers keep it in a function-
-// local static: initialised once, thread-safe, as rx threads may race on
-// their first batches).
-static long env_long(const char *name, long dflt) {
-  const char *e = getenv(name);
-  return e ? atol(e) : dflt;
-}
-
-// An A/B knob: read from the environment in experiment builds only
-// (rx_internal.h kDiag); a product build uses the default.
-#ifdef PPTK_RX_EXPERIMENTS
-#define EXP_KNOB(name, dflt) env_long(name, dflt)
-#else
-#define EXP_KNOB(name, dflt) ((long)(dflt))
-#endif
 
 static uint64_t le64(const uint8_t *p) {
   uint64_t v = 0;
@@ -327,7 +168,8 @@ int pptk_rx_ctx_create(struct pptk_rx_ctx **out, const struct pptk_rx_opts *opts
     c->bpc[v] = rx_variant_blocks_per_cu(v);
     c->tuned[0][v] = c->tuned[1][v] = -1;
   }
-  if (hipMalloc(&c->d_zero, 64) != hipSuccess || hipMemset(c->d_zero, 0, 64) != hipSuccess) {
+  if (hipMalloc(&c->d_zero, 64) != hipSuccess || hipMemset(c->d_zero, 0, 64) != hipSuccess ||
+      !(c->host = host_pipe_create())) {
     (void)hipFree(c->d_zero);
     delete c;
     return -ENOMEM;
@@ -353,38 +195,18 @@ int pptk_rx_ctx_create(struct pptk_rx_ctx **out, const struct pptk_rx_opts *opts
   return 0;
 }
 
-static void free_slot(RxSlot &sl) {
-  if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-  if (sl.done) (void)hipEventDestroy(sl.done);
-  if (sl.stream) (void)hipStreamDestroy(sl.stream);
-  (void)hipHostFree(sl.h_frames);
-  (void)hipHostFree(sl.h_off);
-  (void)hipHostFree(sl.h_len);
-  (void)hipHostFree(sl.h_recs);
-  (void)hipFree(sl.d_frames);
-  (void)hipFree(sl.d_off);
-  (void)hipFree(sl.d_len);
-  (void)hipFree(sl.d_recs);
-  sl = RxSlot();
-}
-
-static void free_staging(pptk_rx_ctx *c) {
-  for (RxSlot &sl : c->slot) free_slot(sl);
-}
-
 void pptk_rx_ctx_destroy(struct pptk_rx_ctx *c) {
   if (!c) return;
   DeviceScope dg(c->device);
   comm_release(c);
   drop_split_streams(c);   // after the communicator that may have used them
-  free_staging(c);
-  delete c->pool;
+  host_pipe_release(c->host);   // the slots, the worker pool
   (void)hipFree(c->d_zero);
   if (c->txpool) {   // its frees are queued on the callers' streams
     (void)hipDeviceSynchronize();
     (void)hipMemPoolDestroy(c->txpool);
   }
-  for (const RxRing &r : c->rings) (void)hipHostUnregister(r.host);
+  host_pipe_destroy(c->host);   // the registered rings, last
   delete c;
 }
 
@@ -1205,580 +1027,5 @@ int pptk_rx_bin_device(struct pptk_rx_ctx *c, const uint16_t *d_len, uint64_t n,
   return hip_err(launch_bin(d_len, n, d_perm, d_scratch, (hipStream_t)stream, kBinGrid,
                             BinDesc{nullptr, 0, nullptr, nullptr}, bin_bounds(), false));
 }
-
-static int ensure_slot(pptk_rx_ctx *c, RxSlot &sl, size_t pkts, size_t bytes) {
-  if (sl.stream && pkts <= sl.cap_pkts && bytes <= sl.cap_bytes) return 0;
-  free_slot(sl);
-  pkts = std::max(pkts, (size_t)c->opts.max_batch);
-  bytes = std::max(bytes, (size_t)c->opts.max_batch * ((c->opts.max_frame + 15) & ~15u)) + 64;
-  if (hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void **)&sl.h_frames, bytes, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void **)&sl.h_off, pkts * 8, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void **)&sl.h_len, pkts * 2, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void **)&sl.h_recs, pkts * 64, hipHostMallocDefault) != hipSuccess ||
-      hipMalloc((void **)&sl.d_frames, bytes) != hipSuccess ||
-      hipMalloc((void **)&sl.d_off, pkts * 8) != hipSuccess ||
-      hipMalloc((void **)&sl.d_len, pkts * 2) != hipSuccess ||
-      hipMalloc((void **)&sl.d_recs, pkts * 64) != hipSuccess) {
-    free_slot(sl);
-    return -ENOMEM;
-  }
-  if (hipHostGetDevicePointer((void **)&sl.hd_frames, sl.h_frames, 0) != hipSuccess ||
-      hipHostGetDevicePointer((void **)&sl.hd_off, sl.h_off, 0) != hipSuccess ||
-      hipHostGetDevicePointer((void **)&sl.hd_len, sl.h_len, 0) != hipSuccess ||
-      hipHostGetDevicePointer((void **)&sl.hd_recs, sl.h_recs, 0) != hipSuccess) {
-    free_slot(sl);
-    return -EIO;
-  }
-  sl.cap_pkts = pkts;
-  sl.cap_bytes = bytes;
-  sl.dev_cap = bytes;
-  return 0;
-}
-
-// Room for a registered-ring span of `bytes` in the slot's device frame
-// buffer (the slot is idle: its last chunk was retired).  Sparse rings
-// (e.g. 2 KB netmap slots) have spans longer than max_batch * max_frame;
-// grown up to 4x the staging size, once.
-static bool fit_span(RxSlot &sl, size_t bytes) {
-  if (bytes <= sl.dev_cap) return true;
-  if (bytes > 4 * sl.cap_bytes) return false;
-  uint8_t *p = nullptr;
-  if (hipMalloc((void **)&p, bytes) != hipSuccess) return false;
-  (void)hipFree(sl.d_frames);
-  sl.d_frames = p;
-  sl.dev_cap = bytes;
-  return true;
-}
-
-// Chunks run "direct" -- the kernel reads the descriptors (and staged
-// frames) from the pinned staging buffers and writes the records into
-// pinned memory over PCIe: one kernel launch per chunk instead of three
-// host-to-device copies, the launch and a device-to-host copy -- when the
-// frames come from a registered ring (the kernel reads them over PCIe
-// anyway) or the staged frame bytes are at most this many.  2 MiB: with
-// four chunks in flight the DMA copy beats the kernel's PCIe reads from
-// there on (1 M-frame C64 calls 375 -> 449 Mpkt/s staged, ring spans
-// 325 -> 408; 4 096-frame C1500 calls 278 -> 238 us), while calls of up to
-// ~1 400 1500-byte frames keep the single launch (DESIGN.md "End-to-end").
-// PPTK_RX_DIRECT_MAX_BYTES overrides.
-static size_t direct_max_bytes() {
-  static const long v = env_long("PPTK_RX_DIRECT_MAX_BYTES", 2l << 20);
-  return v < 0 ? 0 : (size_t)v;
-}
-
-// Bulky staged chunks go down by DMA, but their descriptors and records do
-// not: the kernel reads the 10-byte descriptors from the pinned staging and
-// writes the records into pinned memory over PCIe ("split" chunks), so the
-// copy engine runs nothing but the frame copies back to back -- the two
-// descriptor copies and the record copy cost ~0.18 ms of copy-engine time
-// per 65 536-frame chunk beside its 2.2 ms frame copy (DESIGN.md
-// "End-to-end").  PPTK_RX_SPLIT=0 restores the copies (A/B).
-static bool split_chunks() {
-  static const long v = EXP_KNOB("PPTK_RX_SPLIT", 1);
-  return v != 0;
-}
-
-// A registered ring's chunk whose frames lie densely in the ring (frame
-// bytes >= this fraction of the span they cover) and whose span is above
-// the direct threshold is copied down by DMA as one span instead of being
-// read in place by the kernel: a dense span moves ~48 GB/s of frames that
-// way, the kernel's own reads of host memory ~37-38, so the break-even is
-// near 80 % (1500-byte frames in 2 KB netmap slots, 73 %, measured 37 GB/s
-// by DMA against 38 in place; DESIGN.md "End-to-end").
-// PPTK_RX_RING_DMA_PCT (percent; 0 = always, > 100 = never) overrides.
-static double ring_dma_density() {
-  static const long v = env_long("PPTK_RX_RING_DMA_PCT", 80);
-  return v / 100.0;
-}
-
-// Uniform chunks (every frame one length, ring frames at one stride) run as
-// fixed-stride batches without descriptors (enqueue_chunk).  PPTK_RX_UNIFORM=0
-// turns that off (A/B).
-static bool uniform_chunks() {
-  static const long v = EXP_KNOB("PPTK_RX_UNIFORM", 1);
-  return v != 0;
-}
-
-// Copy one frame into 16-byte-aligned pinned staging with non-temporal
-// stores: the lines go to memory without being read for ownership first
-// and without staying dirty in the host caches, where the copy engine's
-// reads of the staging would have to snoop them.  The bytes past the frame
-// up to the next 16-byte boundary are zero (the kernel never uses them).
-// PPTK_RX_NT_GATHER=0: plain memcpy (A/B).
-static bool nt_gather() {
-  static const long v = EXP_KNOB("PPTK_RX_NT_GATHER", 1);
-  return v != 0;
-}
-
-static void stage_frame(uint8_t *dst, const uint8_t *src, size_t n) {
-  size_t k = 0;
-  for (; k + 16 <= n; k += 16)
-    _mm_stream_si128((__m128i *)(dst + k), _mm_loadu_si128((const __m128i *)(src + k)));
-  if (k < n) {
-    alignas(16) uint8_t t[16] = {0};
-    memcpy(t, src + k, n - k);
-    _mm_stream_si128((__m128i *)(dst + k), _mm_load_si128((const __m128i *)t));
-  }
-}
-
-// The context's worker pool (nullptr with gather_threads <= 1).  If the
-// threads cannot be started the batch runs on the calling thread alone (and
-// later batches try again): no exception leaves the C ABI.
-static WorkerPool *pool_of(pptk_rx_ctx *c) {
-  const size_t nth = std::max<size_t>(1, std::min<size_t>(c->opts.gather_threads, 64));
-  if (nth > 1 && !c->pool) {
-    try {
-      c->pool = new WorkerPool(nth - 1);
-    } catch (...) {
-      c->pool = nullptr;
-    }
-  }
-  return c->pool;
-}
-
-static size_t pool_size(const WorkerPool *pool) { return pool ? pool->size() : 1; }
-
-// Copy n bytes, split over the pool when it pays (a few MB and up; 256 KB
-// pieces measured slower than 1 MB ones on C64 chunks: the pool's per-item
-// cost).
-static void copy_out(WorkerPool *pool, void *dst, const void *src, size_t n) {
-  constexpr size_t kPiece = 1u << 20;
-#ifdef PPTK_RX_SERIAL_COPYOUT
-  pool = nullptr;
-#endif
-  if (!pool || n < 2 * kPiece) {
-    memcpy(dst, src, n);
-    return;
-  }
-  const size_t parts = (n + kPiece - 1) / kPiece;
-  pool->parallel_for(parts, [&](size_t i) {
-    const size_t lo = i * kPiece, hi = std::min(n, lo + kPiece);
-    memcpy((uint8_t *)dst + lo, (const uint8_t *)src + lo, hi - lo);
-  });
-}
-
-// Wait for the slot's chunk and hand its records to the caller.
-static int retire(RxSlot &sl, WorkerPool *pool) {
-  if (!sl.busy) return 0;
-  sl.busy = false;
-  // (HIP spins before it blocks: polling hipEventQuery instead measured
-  // equal on 32-frame chunks)
-  if (hipEventSynchronize(sl.done) != hipSuccess) return -EIO;
-  if (sl.out) copy_out(pool, sl.out, sl.h_recs, sl.count * sl.rec_bytes);
-  return 0;
-}
-
-// The registered ring holding every frame of pkts[0, num), so that frame
-// bytes can be read in place (the kernel reads whole 16-byte chunks, so each
-// frame's chunk-rounded end must lie inside the ring too); NULL otherwise.
-// The registered ring holding the call's first frame, the candidate for
-// reading the frames in place; every chunk checks its own frames against it
-// in its descriptor pass (enqueue_chunk) and is staged instead when one lies
-// outside.  (A serial pass over all frames here, before the first chunk,
-// had cost a 4 M-frame C64 call as much as its frame copies.)
-static const RxRing *ring_of(const pptk_rx_ctx *c, const struct ldp_packet *pkts, int num) {
-  if (c->rings.empty() || num <= 0) return nullptr;
-  const uint8_t *p0 = (const uint8_t *)pkts[0].data;
-  for (const RxRing &r : c->rings)
-    if (p0 >= r.host && p0 < r.host + r.bytes) return &r;
-  return nullptr;
-}
-
-// The registered region holding the caller's whole record array, so that
-// the kernel writes the records there in place over PCIe (no record copy
-// from the staging); NULL otherwise.
-static const RxRing *records_region(const pptk_rx_ctx *c, const void *recs, size_t bytes) {
-  const uint8_t *p = (const uint8_t *)recs;
-  for (const RxRing &r : c->rings)
-    if (p >= r.host && bytes <= r.bytes && (size_t)(p - r.host) <= r.bytes - bytes) return &r;
-  return nullptr;
-}
-
-int pptk_rx_register_ring(struct pptk_rx_ctx *c, void *base, size_t bytes) {
-  if (!c || !base || bytes == 0) return -EINVAL;
-  DeviceScope dg(c->device);
-  if (!dg.ok) return -EIO;
-  if (hipHostRegister(base, bytes, hipHostRegisterMapped) != hipSuccess) return -EIO;
-  void *dev = nullptr;
-  if (hipHostGetDevicePointer(&dev, base, 0) != hipSuccess) {
-    (void)hipHostUnregister(base);
-    return -EIO;
-  }
-  c->rings.push_back(RxRing{(uint8_t *)base, bytes, (const uint8_t *)dev});
-  return 0;
-}
-
-int pptk_rx_unregister_ring(struct pptk_rx_ctx *c, void *base) {
-  if (!c || !base) return -EINVAL;
-  for (size_t i = 0; i < c->rings.size(); ++i) {
-    if (c->rings[i].host == (uint8_t *)base) {
-      DeviceScope dg(c->device);
-  if (!dg.ok) return -EIO;
-      for (RxSlot &sl : c->slot)   // no chunk may still read the ring
-        if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-      (void)hipHostUnregister(base);
-      c->rings.erase(c->rings.begin() + (long)i);
-      return 0;
-    }
-  }
-  return -EINVAL;
-}
-
-// A chunk that failed part-way: nothing it queued may still run (it may
-// read the caller's frames or write the slot) when the error is returned.
-static int chunk_failed(RxSlot &sl, int rc) {
-  (void)hipStreamSynchronize(sl.stream);
-  sl.busy = false;
-  return rc;
-}
-
-// One chunk of a host batch (cnt <= opts.max_batch frames) into slot `sl`,
-// idle and sized by ensure_slot: its descriptors and frames, then its
-// copies, the launch and the record copy-back queued on the slot's stream,
-// nothing waited for.  retire() waits for it and hands the records to `out`.
-// In a registered ring the kernel reads the frames in place over PCIe (or
-// the span goes down by DMA) and only the 10-byte descriptors are written.
-static size_t chunk_bytes(const pptk_rx_ctx *c);
-
-static int enqueue_chunk(pptk_rx_ctx *c, RxSlot &sl, const struct ldp_packet *cp, size_t cnt,
-                         void *out, size_t rec_bytes, const RxRing *ring,
-                         const RxRing *rreg, WorkerPool *pool) {
-  const uint32_t maxf = c->opts.max_frame ? c->opts.max_frame : 65535u;
-  // Descriptors, then the frame bytes.  On one thread (no pool, or a
-  // small chunk) both in one pass.  With the pool, both in parallel over
-  // parts of the chunk: a first pass writes the lengths (and a ring's
-  // offsets) and sums each part's staging bytes, a serial prefix over the
-  // parts gives each part its staging base, and a second pass writes the
-  // staging offsets while it gathers the frames (a serial descriptor pass
-  // had cost a 65 536-frame C64 chunk as much as the whole parallel
-  // gather, DESIGN.md "End-to-end").
-  const bool nt = nt_gather();
-  auto stage = [&sl, cp, nt](size_t i) {
-    if (nt) stage_frame(sl.h_frames + sl.h_off[i], (const uint8_t *)cp[i].data, sl.h_len[i]);
-    else memcpy(sl.h_frames + sl.h_off[i], cp[i].data, sl.h_len[i]);
-  };
-  // one part: lengths (+ ring offsets / span) and, for staged chunks, the
-  // staging bytes it needs; with `base` given, also the staging offsets
-  // and the gather
-  // (write = false: a ring chunk's first pass -- the span, the checks, the
-  // uniformity -- with nothing written; a uniform ring chunk needs no more)
-  auto describe = [&sl, cp, ring, maxf, nt, &stage](size_t i0, size_t i1, size_t base,
-                                                    bool gather, PartDesc &d, bool write = true) {
-    size_t pos = base;
-    if (i1 > i0) {
-      d.p0 = (const uint8_t *)cp[i0].data;
-      d.sz0 = cp[i0].sz;
-      d.stride = i1 - i0 > 1 ? (const uint8_t *)cp[i0 + 1].data - d.p0 : 0;
-      d.same = d.p0 != nullptr && d.sz0 <= maxf;
-      d.uni = d.same;
-    }
-    for (size_t i = i0; i < i1; ++i) {
-      const struct ldp_packet &pk = cp[i];
-      const bool ok = pk.data && pk.sz <= maxf;
-      const uint32_t sz = ok ? pk.sz : 0u;
-      d.same = d.same && ok && pk.sz == d.sz0;
-      d.uni = d.uni && d.same && (const uint8_t *)pk.data == d.p0 + (int64_t)(i - i0) * d.stride;
-      if (write) sl.h_len[i] = (uint16_t)sz;
-      if (ring) {
-        const uint8_t *pd = (const uint8_t *)pk.data;
-        // (every frame's chunk-rounded end inside the registered region)
-        d.outside = d.outside || (pd && (pd < ring->host ||
-                                         (((size_t)(pd - ring->host) + pk.sz + 15) & ~(size_t)15) >
-                                             ring->bytes));
-        const uint64_t o = pd ? (uint64_t)(pd - ring->host) : 0u;
-        if (write) sl.h_off[i] = o;
-        d.lo = std::min<size_t>(d.lo, o);
-        // (the frame's chunk-rounded END, clamped to the region: a span
-        // copy must not read past the registered memory; the kernel's reads
-        // past a frame's end stay inside the span's 16-byte slack)
-        d.hi = std::max<size_t>(d.hi, std::min<size_t>((o + sz + 15) & ~(size_t)15, ring->bytes));
-        d.fbytes += sz;
-      } else if (gather) {
-        sl.h_off[i] = pos;
-        if (sz) stage(i);
-      }
-      pos += (sz + 15) & ~(size_t)15;
-      d.maxlen = std::max(d.maxlen, sz);
-    }
-    d.bytes = pos - base;
-    // this thread's streaming stores, before the copy is queued
-    if (gather && nt) _mm_sfence();
-  };
-  // The pool only for big chunks: waking it costs ~20-40 µs, more than a
-  // 256-frame or even a 1.5 MB gather saves (DESIGN.md "End-to-end").
-  // Staged chunks: parts of ~1024 frames or ~256 KB of frame bytes
-  // (estimated from the first frame), at most 8 per thread, in ONE pass
-  // over the pool -- each
-  // part sums its staging bytes, takes its base from the previous part's
-  // published running total (parts are claimed in order, so that one is
-  // done or in progress), publishes its own, then writes its offsets and
-  // gathers.  Ring chunks (no gather): parts of ~2048 frames.
-  const size_t est = cnt * (size_t)std::min<uint32_t>(cp[0].sz, maxf);
-  const bool staged = !ring;
-  size_t nparts = 1;
-  if (pool && staged && (cnt >= 8192 || est >= (4u << 20)))
-    nparts = std::max(cnt / 1024, est >> 18);
-  else if (pool && !staged && cnt >= 16384)
-    nparts = cnt / 2048;
-  nparts = std::max<size_t>(1, std::min<size_t>(nparts, std::min<size_t>(8 * pool_size(pool), cnt)));
-  std::vector<PartDesc> &parts = sl.parts;
-  parts.assign(nparts, PartDesc{});
-  if (!staged) {
-    // first pass: nothing written; a frame outside the ring stages the
-    // chunk, a uniform chunk needs no descriptors at all
-    auto pass = [&](bool write) {
-      if (nparts == 1)
-        describe(0, cnt, 0, false, parts[0], write);
-      else
-        pool->parallel_for(nparts, [&](size_t t) {
-          parts[t] = PartDesc{};
-          describe(cnt * t / nparts, cnt * (t + 1) / nparts, 0, false, parts[t], write);
-        });
-    };
-    pass(false);
-    bool outside = false, uni = uniform_chunks() && cnt > 1;
-    for (const PartDesc &d : parts) outside = outside || d.outside;
-    if (outside) {   // staged instead (the slot is idle: size its staging)
-      const int rc = ensure_slot(c, sl, std::max<size_t>(c->opts.max_batch, 1), chunk_bytes(c));
-      return rc ? rc : enqueue_chunk(c, sl, cp, cnt, out, rec_bytes, nullptr, rreg, pool);
-    }
-    for (size_t t = 0; t < parts.size() && uni; ++t)
-      uni = parts[t].uni && parts[t].sz0 == parts[0].sz0 && parts[t].stride == parts[0].stride &&
-            parts[t].stride > 0 &&
-            parts[t].p0 == parts[0].p0 + (int64_t)(cnt * t / parts.size()) * parts[0].stride;
-    if (!uni) {
-      for (PartDesc &d : parts) d = PartDesc{};
-      pass(true);
-    }
-  } else if (nparts == 1) {
-    describe(0, cnt, 0, staged, parts[0]);
-  } else {
-    if (sl.run_cap < nparts) {
-      sl.run.reset(new std::atomic<size_t>[nparts]);
-      sl.run_cap = nparts;
-    }
-    std::atomic<size_t> *run = sl.run.get();
-    for (size_t t = 0; t < nparts; ++t) run[t].store(SIZE_MAX, std::memory_order_relaxed);
-    pool->parallel_for(nparts, [&](size_t t) {
-      const size_t i0 = cnt * t / nparts, i1 = cnt * (t + 1) / nparts;
-      PartDesc &d = parts[t];
-      describe(i0, i1, 0, false, d);            // lengths, this part's bytes
-      size_t base = 0;
-      if (t > 0)
-        while ((base = run[t - 1].load(std::memory_order_acquire)) == SIZE_MAX) _mm_pause();
-      run[t].store(base + d.bytes, std::memory_order_release);
-      PartDesc d2{};
-      describe(i0, i1, base, true, d2);         // offsets + gather
-    });
-  }
-  size_t pos = 0, lo = SIZE_MAX, hi = 0, fbytes = 0;
-  uint32_t maxlen = 0;
-  for (const PartDesc &d : parts) {
-    pos += d.bytes;
-    lo = std::min(lo, d.lo);
-    hi = std::max(hi, d.hi);
-    fbytes += d.fbytes;
-    maxlen = std::max(maxlen, d.maxlen);
-  }
-  // Uniform chunk: every frame the same length (and, for a registered ring,
-  // at one fixed stride from the first): it runs as a fixed-stride batch --
-  // no descriptor is read by the kernel (in a staged chunk the frames sit at
-  // 16-byte-rounded offsets, i.e. at a fixed stride already), and frames of
-  // at most 64 bytes take the lane kernel.  A C64 chunk then moves its frames
-  // and its records over PCIe and nothing else.
-  bool uni_len = !parts.empty(), uni_ptr = uni_len;
-  int64_t stride = 0;
-  {
-    const PartDesc &f = parts[0];
-    stride = f.stride;
-    for (size_t t = 0; t < parts.size() && uni_len; ++t) {
-      const PartDesc &d = parts[t];
-      const size_t i0 = cnt * t / parts.size();
-      uni_len = d.same && d.sz0 == f.sz0;
-      // (each part's own stride, and its first frame where the first
-      // part's stride puts it; one-frame parts have no stride of their own)
-      uni_ptr = uni_ptr && uni_len && d.uni &&
-                (d.stride == stride || cnt * (t + 1) / parts.size() - i0 == 1) &&
-                d.p0 == f.p0 + (int64_t)i0 * stride;
-    }
-    if (cnt == 1) uni_ptr = false;
-  }
-  const uint32_t ulen = parts.empty() ? 0u : parts[0].sz0;
-  // a dense ring chunk goes down as one span; the kernel sees the span's
-  // buffer shifted down by `lo`, so the ring offsets stay as they are
-  const bool ring_dma = ring && hi > lo && hi - lo > direct_max_bytes() &&
-                        (double)fbytes >= ring_dma_density() * (double)(hi - lo) &&
-                        fit_span(sl, hi - lo + 16);
-  hipStream_t s = sl.stream;
-  const bool direct =
-      ring ? direct_max_bytes() > 0 && !ring_dma : pos <= direct_max_bytes();
-  // descriptors and records over PCIe, frames by DMA
-  const bool split = !direct && (ring_dma || !ring) && split_chunks();
-  const bool pcie = direct || split;
-  if ((!direct && !ring &&
-       hipMemcpyAsync(sl.d_frames, sl.h_frames, std::max<size_t>(pos, 16),
-                      hipMemcpyHostToDevice, s) != hipSuccess) ||
-      (ring_dma && hipMemcpyAsync(sl.d_frames, ring->host + lo, hi - lo,
-                                  hipMemcpyHostToDevice, s) != hipSuccess) ||
-      (!pcie &&
-       (hipMemcpyAsync(sl.d_off, sl.h_off, cnt * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(sl.d_len, sl.h_len, cnt * 2, hipMemcpyHostToDevice, s) != hipSuccess)))
-    return chunk_failed(sl, -EIO);
-  pptk_rx_dev_batch b;
-  memset(&b, 0, sizeof(b));
-  b.d_frames = ring && !ring_dma ? ring->dev
-               : ring_dma           ? (const uint8_t *)((uintptr_t)sl.d_frames - lo)
-               : direct             ? sl.hd_frames
-                                    : sl.d_frames;
-  b.d_off = pcie ? sl.hd_off : sl.d_off;
-  b.d_len = pcie ? sl.hd_len : sl.d_len;
-  b.max_len = maxlen;
-  b.n = cnt;
-  if (uniform_chunks() && cnt > 1 && uni_len && (!ring || (uni_ptr && stride > 0))) {
-    // fixed stride: staged frames at i * round16(len); ring frames at the
-    // first frame's place + i * stride
-    b.d_off = nullptr;
-    b.d_len = nullptr;
-    b.fixed_len = ulen;
-    if (ring) {
-      b.d_frames += (size_t)(parts[0].p0 - ring->host);
-      b.stride = (uint64_t)stride;
-    } else {
-      b.stride = (ulen + 15u) & ~15u;
-      if (b.stride == 0) b.stride = 16;
-    }
-  }
-  // records: into the caller's array itself when it is registered
-  void *d_out = rreg ? (void *)(rreg->dev + ((const uint8_t *)out - rreg->host))
-                : pcie ? (void *)sl.hd_recs
-                       : (void *)sl.d_recs;
-  if (rec_bytes == 32) b.d_recs32 = (pptk_rx_rec32 *)d_out;   // compact records
-  else b.d_recs = (pptk_rx_rec *)d_out;
-  const int rc = pptk_rx_batch_device(c, &b, s);
-  if (rc != 0) return chunk_failed(sl, rc);
-  if ((!pcie && !rreg &&
-       hipMemcpyAsync(sl.h_recs, sl.d_recs, cnt * rec_bytes, hipMemcpyDeviceToHost, s) !=
-           hipSuccess) ||
-      hipEventRecord(sl.done, s) != hipSuccess)
-    return chunk_failed(sl, -EIO);
-  sl.out = rreg ? nullptr : out;   // (retire copies only staged records)
-  sl.rec_bytes = rec_bytes;
-  sl.count = cnt;
-  sl.busy = true;
-  return 0;
-}
-
-// Slots a synchronous pptk_rx_batch rotates over (chunks in flight; a slot
-// is allocated when a call first has that many chunks): four measured
-// +17-24 % on 1 M-frame C64 calls against two, C1500 +1-2 % (at the PCIe
-// ceiling either way; DESIGN.md "End-to-end").  PPTK_RX_SYNC_SLOTS (2 ..
-// PPTK_RX_MAX_INFLIGHT) overrides.
-static size_t sync_slots() {
-  static const long v = env_long("PPTK_RX_SYNC_SLOTS", PPTK_RX_MAX_INFLIGHT);
-  return (size_t)std::min<long>(std::max<long>(v, 2), PPTK_RX_MAX_INFLIGHT);
-}
-
-// Staging bytes a slot needs for one chunk of this context's batches.
-static size_t chunk_bytes(const pptk_rx_ctx *c) {
-  const uint32_t maxf = c->opts.max_frame ? c->opts.max_frame : 65535u;
-  return std::max<size_t>(c->opts.max_batch, 1) * ((maxf + 15) & ~15u);
-}
-
-static bool host_args_ok(const pptk_rx_ctx *c, const struct ldp_packet *pkts, int num,
-                         const void *recs) {
-  return c && num >= 0 && (num == 0 || (pkts && recs));
-}
-
-// pptk_rx_batch / pptk_rx_batch32: records of rec_bytes (64 or 32) each.
-static int host_batch(struct pptk_rx_ctx *c, const struct ldp_packet *pkts, int num, void *recs,
-                      size_t rec_bytes) {
-  if (!host_args_ok(c, pkts, num, recs)) return -EINVAL;
-  if (num == 0) return 0;
-  if (c->async_n) return -EBUSY;   // the submissions own the slots
-  DeviceScope dg(c->device);
-  if (!dg.ok) return -EIO;
-  WorkerPool *pool = pool_of(c);
-  const RxRing *ring = ring_of(c, pkts, num);
-  const RxRing *rreg = records_region(c, recs, (size_t)num * rec_bytes);
-  const size_t chunk = std::max<size_t>(c->opts.max_batch, 1);
-  int rc = 0;
-  // Multi-buffered: while chunk k runs on one slot's stream (H2D, kernel,
-  // D2H), the host gathers the next chunks into the other slots.
-  const size_t nslots = sync_slots();
-  size_t k = 0, cnt = 0;
-  for (size_t first = 0; first < (size_t)num && rc == 0; first += cnt, ++k) {
-    RxSlot &sl = c->slot[k % nslots];
-    if ((rc = retire(sl, pool)) != 0) break;
-    cnt = std::min(chunk, (size_t)num - first);
-    if ((rc = ensure_slot(c, sl, chunk, ring ? 64 : chunk_bytes(c))) != 0) break;
-    rc = enqueue_chunk(c, sl, pkts + first, cnt, (uint8_t *)recs + first * rec_bytes, rec_bytes,
-                       ring, rreg, pool);
-  }
-  // drain (also on error: nothing may still read the caller's buffers)
-  for (RxSlot &sl : c->slot) {
-    const int r2 = retire(sl, pool);
-    if (rc == 0) rc = r2;
-  }
-  return rc;
-}
-
-int pptk_rx_batch(struct pptk_rx_ctx *c, const struct ldp_packet *pkts, int num,
-                  struct pptk_rx_rec *recs) {
-  return host_batch(c, pkts, num, recs, sizeof(pptk_rx_rec));
-}
-
-int pptk_rx_batch32(struct pptk_rx_ctx *c, const struct ldp_packet *pkts, int num,
-                    struct pptk_rx_rec32 *recs) {
-  return host_batch(c, pkts, num, recs, sizeof(pptk_rx_rec32));
-}
-
-static int host_submit(struct pptk_rx_ctx *c, const struct ldp_packet *pkts, int num, void *recs,
-                       size_t rec_bytes) {
-  if (!host_args_ok(c, pkts, num, recs)) return -EINVAL;
-  if (num == 0) return 0;
-  if ((size_t)num > std::max<size_t>(c->opts.max_batch, 1)) return -EINVAL;
-  if (c->async_n >= PPTK_RX_MAX_INFLIGHT) return -EBUSY;
-  DeviceScope dg(c->device);
-  if (!dg.ok) return -EIO;
-  const RxRing *ring = ring_of(c, pkts, num);
-  const RxRing *rreg = records_region(c, recs, (size_t)num * rec_bytes);
-  // the slots rotate in submission order (FIFO), so consecutive
-  // submissions run on different streams and may overlap on the GPU
-  RxSlot &sl = c->slot[(c->async_head + c->async_n) % PPTK_RX_MAX_INFLIGHT];
-  int rc = ensure_slot(c, sl, std::max<size_t>(c->opts.max_batch, 1), ring ? 64 : chunk_bytes(c));
-  if (rc == 0)
-    rc = enqueue_chunk(c, sl, pkts, (size_t)num, recs, rec_bytes, ring, rreg, pool_of(c));
-  if (rc != 0) return rc;
-  ++c->async_n;
-  return 0;
-}
-
-int pptk_rx_batch_submit(struct pptk_rx_ctx *c, const struct ldp_packet *pkts, int num,
-                         struct pptk_rx_rec *recs) {
-  return host_submit(c, pkts, num, recs, sizeof(pptk_rx_rec));
-}
-
-int pptk_rx_batch_submit32(struct pptk_rx_ctx *c, const struct ldp_packet *pkts, int num,
-                           struct pptk_rx_rec32 *recs) {
-  return host_submit(c, pkts, num, recs, sizeof(pptk_rx_rec32));
-}
-
-int pptk_rx_batch_complete(struct pptk_rx_ctx *c) {
-  if (!c) return -EINVAL;
-  if (c->async_n == 0) return -ENOENT;
-  DeviceScope dg(c->device);
-  if (!dg.ok) return -EIO;
-  RxSlot &sl = c->slot[c->async_head];
-  const int cnt = (int)sl.count;
-  const int rc = retire(sl, c->pool);
-  // (dropped from the queue even on an error: its slot is idle again)
-  c->async_head = (c->async_head + 1) % PPTK_RX_MAX_INFLIGHT;
-  --c->async_n;
-  return rc ? rc : cnt;
-}
-
-int pptk_rx_batch_pending(const struct pptk_rx_ctx *c) { return c ? c->async_n : -EINVAL; }
 
 }  // extern "C"

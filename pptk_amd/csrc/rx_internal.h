@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <atomic>
 
@@ -37,6 +38,25 @@ uint32_t ctx_comm_timeout_ms(const pptk_rx_ctx *c);   // opts.comm_timeout_ms (0
 int ctx_coll_cap(const pptk_rx_ctx *c);
 void comm_release(pptk_rx_ctx *c);   // destroys the context's communicator, if any
 
+// ... and with the host batch pipeline (rx_host.hip), whose state the context
+// owns as one opaque member.  pptk_rx_ctx_destroy releases it in two steps:
+// the slots and the worker pool first; the registered rings, and the state
+// itself, only after the context's other device memory is gone.
+struct HostPipe;
+const pptk_rx_opts &ctx_opts(const pptk_rx_ctx *c);
+HostPipe *ctx_host_pipe(const pptk_rx_ctx *c);
+HostPipe *host_pipe_create();   // nullptr: no memory
+void host_pipe_release(HostPipe *hp);
+void host_pipe_destroy(HostPipe *hp);
+
+// An integer environment knob, read once (the callers keep it in a function-
+// local static: initialised once, thread-safe, as rx threads may race on
+// their first batches).
+inline long env_long(const char *name, long dflt) {
+  const char *e = getenv(name);
+  return e ? atol(e) : dflt;
+}
+
 // Diagnostic tune bits (RxKArgs::tune 3, 4, 7, 9: skip record stores, the
 // per-frame phase, half the record bytes, the tx writes -- output invalid,
 // for profiling) and the A/B environment knobs of the host code exist only
@@ -47,6 +67,13 @@ void comm_release(pptk_rx_ctx *c);   // destroys the context's communicator, if 
 constexpr bool kDiag = true;
 #else
 constexpr bool kDiag = false;
+#endif
+// An A/B knob: read from the environment in experiment builds only; a product
+// build uses the default.
+#ifdef PPTK_RX_EXPERIMENTS
+#define EXP_KNOB(name, dflt) env_long(name, dflt)
+#else
+#define EXP_KNOB(name, dflt) ((long)(dflt))
 #endif
 
 // Kernel arguments (by value; a handful of SGPRs).
