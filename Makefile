@@ -14,7 +14,7 @@ LIB := pptk_amd/libpptkrx.so
 HIP_SRCS := pptk_amd/csrc/rx_kernel.hip pptk_amd/csrc/rx_bin.hip pptk_amd/csrc/rx_permit.hip \
             pptk_amd/csrc/rx_capi.hip pptk_amd/csrc/rx_comm.hip pptk_amd/csrc/rx_ring.hip \
             pptk_amd/csrc/tx_frag.hip pptk_amd/csrc/tx_tunnel.hip pptk_amd/csrc/tx_hdr.hip \
-            pptk_amd/csrc/rx_flow.hip pptk_amd/csrc/rx_host.hip
+            pptk_amd/csrc/rx_flow.hip pptk_amd/csrc/rx_flowstat.hip pptk_amd/csrc/rx_host.hip
 C_SRCS := pptk_amd/csrc/host/ipcksum.c pptk_amd/csrc/host/hashseed.c pptk_amd/csrc/host/tcpopt.c \
           pptk_amd/csrc/host/iphash.c pptk_amd/csrc/host/timerlink.c pptk_amd/csrc/host/ipfrag.c \
           pptk_amd/csrc/host/tcpseq.c pptk_amd/csrc/host/tunnel.c pptk_amd/csrc/host/flowtab.c
@@ -61,12 +61,13 @@ all: $(HOOKS_LIB)
 # A/B builds of the product library with extra defines, e.g.
 #   make abvariant NAME=full DEFS=-DPPTK_RX_FULL_UNROLL
 #   make abvariant NAME=flow4 DEFS=-DPPTK_FLOW_TEAM=4   (rx_flow.hip: four lanes per record)
+#   make abvariant NAME=flowstat_direct DEFS=-DPPTK_FLOWSTAT_DIRECT=1   (rx_flowstat.hip: no LDS stage)
 abvariant:
 	$(MAKE) OBJDIR=build/ab_$(NAME)/obj LIB=build/ab_$(NAME)/libpptkrx.so \
 	  HIPFLAGS="$(HIPFLAGS) $(DEFS)" build/ab_$(NAME)/libpptkrx.so
 
 # the kernel files' assembly and resource tables (build/asm/<file>.resource.txt)
-ASM_SRCS := rx_kernel tx_hdr
+ASM_SRCS := rx_kernel tx_hdr rx_flowstat
 asm: $(HIP_SRCS)
 	@mkdir -p build/asm
 	cd build/asm && for f in $(ASM_SRCS); do $(HIPCC) $(HIPFLAGS) -I../../include -c ../../pptk_amd/csrc/$$f.hip -save-temps -o $$f.o -Rpass-analysis=kernel-resource-usage 2> $$f.resource.txt; done; true

@@ -793,10 +793,12 @@ uint32_t pptk_tunnel_decap_host(const void *frame, uint32_t len, uint32_t *in_of
  * pptk_flow_lookup_host is the same rule over the host image (idx required,
  * subject and status nullable) and the CPU statement of this contract.
  *
- * Out of scope: inserts or deletes performed by a kernel, growth, idle expiry
- * or last-seen stamps, per-flow counters, a direction-symmetric key (the
- * caller inserts both directions), pptk_rx_rec32 input (it lacks the IPv6
- * addresses), and locking. */
+ * Last-seen stamps, per-flow counters and idle expiry are the next section,
+ * "Flow state".
+ *
+ * Out of scope: inserts or deletes performed by a kernel, growth, a
+ * direction-symmetric key (the caller inserts both directions),
+ * pptk_rx_rec32 input (it lacks the IPv6 addresses), and locking. */
 struct pptk_flow_key {            /* 40 bytes: the tuple the flow hash covers */
   uint8_t src[16], dst[16];       /* as pptk_rx_rec.src / .dst                */
   uint16_t sport, dport;          /* host order, as the record                */
@@ -832,6 +834,102 @@ int pptk_flow_lookup_device(struct pptk_rx_ctx *ctx, const struct pptk_flow_tabl
                             void *stream);
 int pptk_flow_lookup_host(const struct pptk_flow_table *t, const struct pptk_rx_rec *recs,
                           uint64_t n, const uint8_t *subject, uint32_t *idx, uint8_t *status);
+
+/* Flow state: what the frames of a batch leave behind per flow, and what the
+ * host does with it.  The batches never leave device memory, so the host
+ * sees no traffic; a kernel leaves per flow value a packet counter, a byte
+ * counter and a last-seen stamp, the host downloads that small array now and
+ * then and deletes the flows that have been idle -- the work the reference
+ * does in its table users (ldp/ldpswitch.c:88-123 time_out(): every entry
+ * with e->time64 + TIMEOUT < time64, the stamp refreshed per packet at :139;
+ * arp/arp.c:30-31,107-120: a 30 s entry timer).  The gateway loop is
+ *   insert + stats_reset, then per batch
+ *   rx -> pptk_flow_lookup_device -> pptk_flow_account_device
+ *      -> pptk_tx_rewrite_flow_device / seq-translate / encap -> fragment,
+ *   and every T seconds: download stats -> pptk_flow_table_expire
+ *      -> stats_reset of the recycled values -> pptk_flow_table_sync.
+ *
+ * Accounting.  Entry v of the stats array belongs to flow value v (the value
+ * given at insert, d_idx[i] of the lookup).  pptk_flow_account_host is the
+ * CPU statement of the contract: for frame i, v = idx[i], L = len ? len[i] :
+ * fixed_len, e = v < stats_count ? &stats[v] : unmatched; if e is not NULL,
+ *   e->packets += 1; e->bytes += L; e->last_seen = max(e->last_seen, now).
+ * The arrays accumulate (the caller zeroes them once); PPTK_FLOW_NONE is an
+ * index >= stats_count like any other, so the lookup's non-subjects and
+ * misses land in `unmatched` (nullable), the drop counter.  `reserved` and
+ * every entry at or past stats_count are never touched; n = 0 changes nothing
+ * and launches nothing.  The sums are integer arithmetic mod 2^64 and
+ * independent of order: the device call equals the host call bit for bit,
+ * whatever streams or kernel shapes ran it.  `now` is the caller's clock in
+ * the caller's unit.  -EINVAL: a null ctx (device call); null idx or stats
+ * with n > 0; stats_count 0 or above 2^32; idx not 4-byte, len not 2-byte,
+ * stats or unmatched not 32-byte aligned; fixed_len > 65535 (with or without
+ * len).  The device call is asynchronous on `stream`; calls on several
+ * streams may add into one array.
+ *
+ * pptk_flow_stats_reset_device sets stats[v] = {0, 0, now, reserved
+ * unchanged} for every v = d_values[k] < stats_count (values past the array
+ * are skipped, duplicates are allowed) with plain stores in one launch: how a
+ * flow value is recycled, and how a flow inserted before its first frame gets
+ * a stamp, so that it does not expire at once.  It must not run beside an
+ * accounting call that counts the same values.  -EINVAL as above, d_values
+ * 4-byte aligned and non-null with count > 0.
+ *
+ * pptk_flow_account_shape reports the accounting kernel of the built
+ * library: the frames a workgroup sums in LDS before it touches the array
+ * (segment_frames) and the slots of its LDS table (lds_slots; 0 for a build
+ * whose lanes add to the array directly, make abvariant NAME=flowstat_direct
+ * DEFS=-DPPTK_FLOWSTAT_DIRECT=1).  Results do not depend on it.
+ *
+ * pptk_flow_table_expire (host; works on host-only tables) deletes from the
+ * host image every flow whose value v < stats_count and whose
+ * stats[v].last_seen + idle < now -- strictly, as ldpswitch.c:100, and without
+ * 64-bit wrap: a sum past 2^64 is "not idle".  `stats` is the host copy the
+ * caller downloaded.  Flows whose value lies past stats_count never expire.
+ * At most `cap` flows are deleted per call, their values written to
+ * expired_values (nullable when cap is 0, and then nothing is deleted); the
+ * return value is the number deleted, and the caller calls again while it
+ * equals cap.  Deletion is the table's backward-shift delete and marks the
+ * same dirty pages, so the next sync uploads them; probe_limit stays a valid
+ * bound.  -EINVAL for a null t or stats, or a null expired_values with cap > 0.
+ *
+ * pptk_tx_rewrite_flow_device is pptk_tx_rewrite_device with the lookup's
+ * result: with d_idx non-null frame i takes d_rw[d_idx[i]], and an index >=
+ * rw_count means no flow -- the frame is neither read nor written and its
+ * status is exactly PPTK_RW_ST_NOFLOW (pptk_tcp_seq_translate_device's rule);
+ * rw_count must not be 0 and d_idx must be 4-byte aligned.  With d_idx NULL
+ * it is pptk_tx_rewrite_device itself (rw_count 1 or n).  Everything else is
+ * that call's contract.
+ *
+ * Out of scope: TCP-state tracking (FIN / RST), per-flow rate limiting, an
+ * LRU list, IPv6 address rewrite (the reference has no such setter),
+ * pptk_rx_rec32 input, and locking. */
+struct pptk_flow_stats {     /* 32 bytes, 32-byte aligned; entry v belongs to flow value v */
+  uint64_t packets;          /* frames counted, mod 2^64                      */
+  uint64_t bytes;            /* sum of their descriptor lengths, mod 2^64     */
+  uint64_t last_seen;        /* max of `now` over the calls that counted or reset it */
+  uint64_t reserved;         /* never read, never written                     */
+};
+#define PPTK_RW_ST_NOFLOW 0x80u    /* d_idx[i] >= rw_count: frame left untouched */
+
+int pptk_flow_account_device(struct pptk_rx_ctx *ctx, const uint32_t *d_idx,
+                             const uint16_t *d_len, uint32_t fixed_len, uint64_t n,
+                             struct pptk_flow_stats *d_stats, uint64_t stats_count,
+                             struct pptk_flow_stats *d_unmatched, uint64_t now, void *stream);
+int pptk_flow_account_host(const uint32_t *idx, const uint16_t *len, uint32_t fixed_len,
+                           uint64_t n, struct pptk_flow_stats *stats, uint64_t stats_count,
+                           struct pptk_flow_stats *unmatched, uint64_t now);
+int pptk_flow_stats_reset_device(struct pptk_rx_ctx *ctx, struct pptk_flow_stats *d_stats,
+                                 uint64_t stats_count, const uint32_t *d_values, uint64_t count,
+                                 uint64_t now, void *stream);
+void pptk_flow_account_shape(uint32_t *segment_frames, uint32_t *lds_slots);
+int pptk_flow_table_expire(struct pptk_flow_table *t, const struct pptk_flow_stats *stats,
+                           uint64_t stats_count, uint64_t now, uint64_t idle,
+                           uint32_t *expired_values, uint32_t cap);
+int pptk_tx_rewrite_flow_device(struct pptk_rx_ctx *ctx, uint8_t *d_frames, const uint64_t *d_off,
+                                const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
+                                uint64_t n, const struct pptk_rewrite *d_rw, uint64_t rw_count,
+                                const uint32_t *d_idx, uint8_t *d_status, void *stream);
 
 /* Tuning: force kernel variant `variant` (0 .. pptk_rx_variant_count()-1)
  * and/or memory-policy flags for every later batch of this context; -1

@@ -2,7 +2,10 @@
  * flowtab.c -- the host half of the flow table (include/pptk_rx.h "Flow
  * table"): the slot image and its insert, update, delete, find, clear and
  * stats, the dirty-page bitmap pptk_flow_table_sync uploads from, and
- * pptk_flow_lookup_host, the CPU statement of the device lookup.  The
+ * pptk_flow_lookup_host, the CPU statement of the device lookup; and the
+ * host half of "Flow state": pptk_flow_table_expire, which deletes idle flows
+ * by a downloaded stats array, and pptk_flow_account_host, the CPU statement
+ * of the accounting kernel (rx_flowstat.hip).  The
  * structure is the reference's hashtable/hashtable.h -- a power-of-two array
  * addressed by hashval & (bucketcnt - 1), never growing -- with the bucket's
  * candidate list laid out in the array itself (linear probing), so that the
@@ -195,20 +198,29 @@ int pptk_flow_table_update(struct pptk_flow_table *t, const struct pptk_flow_key
   return 0;
 }
 
+static void delete_at(struct pptk_flow_table *t, uint32_t hole);
+
 int pptk_flow_table_delete(struct pptk_flow_table *t, const struct pptk_flow_key *key,
                            uint64_t flow_hash)
 {
-  const uint32_t mask = t ? t->slots - 1 : 0;
-  uint32_t hole, j;
+  uint32_t hole;
   int found;
   if (!t || !key_ok(key))
     return -EINVAL;
   hole = probe(t, key, flow_hash, &found);
   if (!found)
     return -ENOENT;
-  /* backward shift: every entry of the cluster behind the hole whose home
-   * slot does not lie in (hole, j] moves into the hole, so that no probe
-   * meets an unused slot before its key */
+  delete_at(t, hole);
+  return 0;
+}
+
+/* Empties the used slot `hole`.  Backward shift: every entry of the cluster
+ * behind the hole whose home slot does not lie in (hole, j] moves into the
+ * hole, so that no probe meets an unused slot before its key. */
+static void delete_at(struct pptk_flow_table *t, uint32_t hole)
+{
+  const uint32_t mask = t->slots - 1;
+  uint32_t j;
   for (j = (hole + 1) & mask; t->img[j].used; j = (j + 1) & mask) {
     const uint32_t from_home = (j - home_of(t, t->img[j].hash)) & mask;
     if (from_home >= ((j - hole) & mask)) {
@@ -220,6 +232,63 @@ int pptk_flow_table_delete(struct pptk_flow_table *t, const struct pptk_flow_key
   memset(&t->img[hole], 0, sizeof(t->img[hole]));
   mark(t, hole);
   t->count--;
+}
+
+/* Idle expiry (include/pptk_rx.h "Flow state").  The walk visits the slots
+ * in array order and stays on a slot while it deletes there: the backward
+ * shift may have put another entry into it.  An entry the walk has not yet
+ * seen lies in a slot after the walk's, and a shift only ever moves it back
+ * as far as the slot being emptied -- the walk's own; the slots a cluster
+ * that wraps round the end of the array shifts within [0, walk) hold entries
+ * the walk has already kept.  So one pass sees every entry. */
+int pptk_flow_table_expire(struct pptk_flow_table *t, const struct pptk_flow_stats *stats,
+                           uint64_t stats_count, uint64_t now, uint64_t idle,
+                           uint32_t *expired_values, uint32_t cap)
+{
+  uint32_t s, done = 0;
+  if (!t || !stats || (cap && !expired_values))
+    return -EINVAL;
+  if (cap > 0x7fffffffu)
+    cap = 0x7fffffffu;   /* the count is returned as an int */
+  for (s = 0; s < t->slots && done < cap; s++) {
+    while (t->img[s].used && done < cap) {
+      const uint32_t v = t->img[s].value;
+      uint64_t seen;
+      if (v >= stats_count)
+        break;
+      seen = stats[v].last_seen;
+      /* seen + idle < now, without the sum */
+      if (!(now > seen && now - seen > idle))
+        break;
+      expired_values[done++] = v;
+      delete_at(t, s);
+    }
+  }
+  return (int)done;
+}
+
+int pptk_flow_account_host(const uint32_t *idx, const uint16_t *len, uint32_t fixed_len,
+                           uint64_t n, struct pptk_flow_stats *stats, uint64_t stats_count,
+                           struct pptk_flow_stats *unmatched, uint64_t now)
+{
+  uint64_t i;
+  if (stats_count == 0 || stats_count > (1ull << 32) || fixed_len > 65535u)
+    return -EINVAL;
+  if (((uintptr_t)idx & 3u) || ((uintptr_t)len & 1u) || ((uintptr_t)stats & 31u) ||
+      ((uintptr_t)unmatched & 31u))
+    return -EINVAL;
+  if (n && (!idx || !stats))
+    return -EINVAL;
+  for (i = 0; i < n; i++) {
+    const uint32_t v = idx[i];
+    struct pptk_flow_stats *e = v < stats_count ? &stats[v] : unmatched;
+    if (!e)
+      continue;
+    e->packets += 1;
+    e->bytes += len ? len[i] : fixed_len;
+    if (e->last_seen < now)
+      e->last_seen = now;
+  }
   return 0;
 }
 

@@ -735,10 +735,20 @@ int pptk_tx_rewrite_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint6
                            const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
                            uint64_t n, const struct pptk_rewrite *d_rw, uint64_t rw_count,
                            uint8_t *d_status, void *stream) {
-  const bool ok = d_rw && (rw_count == 1 || rw_count == n);
+  return pptk_tx_rewrite_flow_device(c, d_frames, d_off, d_len, stride, fixed_len, n, d_rw,
+                                     rw_count, nullptr, d_status, stream);
+}
+
+int pptk_tx_rewrite_flow_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_t *d_off,
+                                const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
+                                uint64_t n, const struct pptk_rewrite *d_rw, uint64_t rw_count,
+                                const uint32_t *d_idx, uint8_t *d_status, void *stream) {
+  const bool ok = d_rw && (d_idx ? rw_count != 0 && !((uintptr_t)d_idx & 3u)
+                                 : rw_count == 1 || rw_count == n);
   return hdr_op(c, d_frames, d_off, d_len, stride, fixed_len, n, d_status, ok,
                 [&](const HdrBatch &b, int grid) {
-                  const RewriteKArgs a = {b, d_rw, rw_count == 1 ? 1u : 0u};
+                  const RewriteKArgs a = {b, d_rw, !d_idx && rw_count == 1 ? 1u : 0u, d_idx,
+                                          rw_count};
                   return launch_rewrite(a, grid, (hipStream_t)stream);
                 });
 }

@@ -202,11 +202,13 @@ struct HdrBatch {
   uint32_t fixed_len;
   uint8_t *status;       // nullable: per-frame status byte
 };
-// header rewrite (pptk_tx_rewrite_device): rw[rw_one ? 0 : i]
+// header rewrite (pptk_tx_rewrite_device, pptk_tx_rewrite_flow_device)
 struct RewriteKArgs {
   HdrBatch b;
   const pptk_rewrite *rw;
   uint32_t rw_one;
+  const uint32_t *idx;   // nullable -> rw[rw_one ? 0 : i]; else rw[idx[i]]
+  uint64_t rw_count;     // with idx: an index at or past it is "no flow"
 };
 // MSS clamping (pptk_tcp_mss_clamp_device): new MSS, PPTK_MSS_* flags
 struct MssKArgs {

@@ -147,6 +147,11 @@ __global__ __launch_bounds__(256) void rx_rewrite_kernel(RewriteKArgs a) {
   LDS_AS uint8_t *slot = lane_slot<RW_SLOT>();
   const uint64_t step = (uint64_t)gridDim.x * 256u;
   for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.b.n; i += step) {
+    const uint64_t j = a.idx ? (uint64_t)a.idx[i] : (a.rw_one ? 0u : i);
+    if (a.idx && j >= a.rw_count) {   // no flow: the frame is not even read
+      if (a.b.status) a.b.status[i] = (uint8_t)PPTK_RW_ST_NOFLOW;
+      continue;
+    }
     const LaneFrame fr = load_frame<RW_SLOT>(a.b, i, slot);
     const uint64_t base = fr.base;
     const uint32_t len = fr.len;
@@ -155,7 +160,7 @@ __global__ __launch_bounds__(256) void rx_rewrite_kernel(RewriteKArgs a) {
     const Parse p = parse_frame(v, len);
     uint32_t st = 0;
     if ((p.flags & (PPTK_RX_F_PARSED | PPTK_RX_F_MALFORMED | PPTK_RX_F_IPV6)) == PPTK_RX_F_PARSED) {
-      const pptk_rewrite w = a.rw[a.rw_one ? 0 : i];
+      const pptk_rewrite w = a.rw[j];
       const int l3 = (int)p.l3, l4 = (int)p.rs;
       const bool l4ok = p.flags & PPTK_RX_F_L4;
       const uint32_t proto = p.proto;

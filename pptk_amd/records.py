@@ -30,6 +30,7 @@ REWRITE_DTYPE = np.dtype([("ops", "<u4"), ("src", "<u4"), ("dst", "<u4"),
 assert REWRITE_DTYPE.itemsize == 16
 RW_DECR_TTL, RW_SRC, RW_DST, RW_SPORT, RW_DPORT = 0x1, 0x2, 0x4, 0x8, 0x10
 RW_ST_IP, RW_ST_L4, RW_ST_TTL_ZERO, RW_ST_EXPIRED, RW_ST_ICMP = 0x1, 0x2, 0x4, 0x8, 0x10
+RW_ST_NOFLOW = 0x80   # pptk_tx_rewrite_flow_device: idx[i] >= rw_count, frame untouched
 RW_ICMP_ID = 0x20
 MSS_SYN_ONLY = 0x1
 MSS_ST_TCP, MSS_ST_FOUND, MSS_ST_CLAMPED, MSS_ST_BADOPT = 0x1, 0x2, 0x4, 0x8
@@ -62,6 +63,10 @@ FLOW_KEY_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16), ("sport", "<u2"
 assert FLOW_KEY_DTYPE.itemsize == 40
 FLOW_NONE = 0xFFFFFFFF
 FLOW_ST_SUBJECT, FLOW_ST_HIT = 0x1, 0x2
+# struct pptk_flow_stats (include/pptk_rx.h "Flow state"): entry v belongs to flow value v
+FLOW_STATS_DTYPE = np.dtype([("packets", "<u8"), ("bytes", "<u8"), ("last_seen", "<u8"),
+                             ("reserved", "<u8")])
+assert FLOW_STATS_DTYPE.itemsize == 32
 
 REC32_DTYPE = np.dtype([
     ("flow_hash", "<u8"),

@@ -188,6 +188,8 @@ EXPORTS = ("pptk_rx_opts_default", "pptk_rx_ctx_create", "pptk_rx_ctx_destroy",
            "pptk_flow_table_delete", "pptk_flow_table_find", "pptk_flow_table_insert_recs",
            "pptk_flow_table_clear", "pptk_flow_table_stats", "pptk_flow_table_sync",
            "pptk_flow_lookup_device", "pptk_flow_lookup_host",
+           "pptk_flow_account_device", "pptk_flow_account_host", "pptk_flow_stats_reset_device",
+           "pptk_flow_account_shape", "pptk_flow_table_expire", "pptk_tx_rewrite_flow_device",
            "pptk_rx_autotune", "pptk_rx_place_records",
            "pptk_rx_place_buffers", "pptk_rx_ring_alloc", "pptk_rx_ring_free",
            "pptk_rx_gather_alloc", "pptk_rx_gather_free",
@@ -350,6 +352,21 @@ def lib(path=None):
             L.pptk_flow_lookup_device.restype = ctypes.c_int
             L.pptk_flow_lookup_host.argtypes = [vp, vp, u64, vp, vp, vp]
             L.pptk_flow_lookup_host.restype = ctypes.c_int
+        if hasattr(L, "pptk_flow_account_device"):     # absent from older A/B builds
+            u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+            L.pptk_flow_account_device.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, u64, vp]
+            L.pptk_flow_account_device.restype = ctypes.c_int
+            L.pptk_flow_account_host.argtypes = [vp, vp, u32, u64, vp, u64, vp, u64]
+            L.pptk_flow_account_host.restype = ctypes.c_int
+            L.pptk_flow_stats_reset_device.argtypes = [vp, vp, u64, vp, u64, u64, vp]
+            L.pptk_flow_stats_reset_device.restype = ctypes.c_int
+            L.pptk_flow_account_shape.argtypes = [ctypes.POINTER(u32), ctypes.POINTER(u32)]
+            L.pptk_flow_account_shape.restype = None
+            L.pptk_flow_table_expire.argtypes = [vp, vp, u64, u64, u64, vp, u32]
+            L.pptk_flow_table_expire.restype = ctypes.c_int
+            L.pptk_tx_rewrite_flow_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, u64, vp,
+                                                      vp, vp]
+            L.pptk_tx_rewrite_flow_device.restype = ctypes.c_int
         if hasattr(L, "pptk_rx_permit_device"):        # absent from older A/B builds
             L.pptk_rx_permit_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
             L.pptk_rx_permit_scratch_bytes.restype = ctypes.c_size_t
@@ -738,6 +755,24 @@ class RxContext:
         if rc != 0:
             raise OSError(-rc, f"pptk_tx_rewrite_device failed ({rc})")
 
+    def tx_rewrite_flow_device(self, frames, n, rw, idx=None, off=None, lens=None, stride=0,
+                               fixed_len=0, status=None, stream=None):
+        """pptk_tx_rewrite_flow_device: tx_rewrite_device with rw a table of
+        struct pptk_rewrite entries indexed by idx (torch int32 CUDA tensor of
+        n entries, the idx of flow_lookup_device; an index at or past the
+        table, -1 = FLOW_NONE among them, leaves the frame alone with status
+        records.RW_ST_NOFLOW).  idx=None is tx_rewrite_device itself."""
+        import torch
+        if not hasattr(self._L, "pptk_tx_rewrite_flow_device"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_tx_rewrite_flow_device")
+        count = rw.numel() * rw.element_size() // 16
+        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+        rc = self._L.pptk_tx_rewrite_flow_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
+                                                 stride, fixed_len, n, _dp(rw), count, _dp(idx),
+                                                 _dp(status), ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_tx_rewrite_flow_device failed ({rc})")
+
     def mss_clamp_device(self, frames, n, mss, syn_only=False, off=None, lens=None, stride=0,
                          fixed_len=0, status=None, stream=None):
         """TCP MSS clamping with incremental checksum update, in place and
@@ -909,6 +944,42 @@ class RxContext:
         if rc != 0:
             raise OSError(-rc, f"pptk_flow_lookup_device failed ({rc})")
         return idx, status
+
+    def flow_account_device(self, idx, stats, now, lens=None, fixed_len=0, unmatched=None,
+                            n=None, stream=None):
+        """pptk_flow_account_device, asynchronous: adds the n frames of idx
+        (torch int32 CUDA tensor, the idx of flow_lookup_device) to stats, a
+        CUDA tensor of struct pptk_flow_stats entries (32 bytes each,
+        records.FLOW_STATS_DTYPE; entry v belongs to flow value v), with
+        their lengths lens (int16 CUDA tensor, the C array's uint16 bits) or
+        fixed_len, and stamps the entries with `now`.  Frames whose index is
+        at or past the array go to unmatched (one entry, optional).  The
+        tensors accumulate: the caller zeroes them once."""
+        import torch
+        if not hasattr(self._L, "pptk_flow_account_device"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_flow_account_device")
+        n = idx.numel() if n is None else n
+        count = stats.numel() * stats.element_size() // 32
+        s = stream if stream is not None else torch.cuda.current_stream(stats.device)
+        rc = self._L.pptk_flow_account_device(self._ctx, _dp(idx), _dp(lens), fixed_len, n,
+                                              _dp(stats), count, _dp(unmatched), now,
+                                              ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_account_device failed ({rc})")
+
+    def flow_stats_reset_device(self, stats, values, now, stream=None):
+        """pptk_flow_stats_reset_device, asynchronous: stats[v] = {0, 0, now}
+        for every v of values (torch int32 CUDA tensor) inside the array."""
+        import torch
+        if not hasattr(self._L, "pptk_flow_stats_reset_device"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_flow_stats_reset_device")
+        count = stats.numel() * stats.element_size() // 32
+        s = stream if stream is not None else torch.cuda.current_stream(stats.device)
+        rc = self._L.pptk_flow_stats_reset_device(self._ctx, _dp(stats), count, _dp(values),
+                                                  values.numel(), now,
+                                                  ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_stats_reset_device failed ({rc})")
 
     # ---- multi-GPU (RCCL) -------------------------------------------------
     def comm_create(self, nranks, rank, uid):
@@ -1186,6 +1257,23 @@ class FlowTable:
             raise OSError(-rc, f"pptk_flow_table_sync failed ({rc})")
         return up.value
 
+    def expire(self, stats, now, idle, cap=None):
+        """pptk_flow_table_expire: deletes up to cap (default: all) flows whose
+        value v lies inside stats -- a NumPy array of records.FLOW_STATS_DTYPE,
+        the downloaded copy -- with stats[v].last_seen + idle < now, and
+        returns their values (uint32).  Call again while it returns cap
+        values; sync() uploads the change."""
+        if not hasattr(self._L, "pptk_flow_table_expire"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_flow_table_expire")
+        st = _flow_stats(stats)
+        cap = self.stats()["count"] if cap is None else cap
+        out = np.zeros(max(cap, 1), np.uint32)
+        rc = self._L.pptk_flow_table_expire(self._t, st.ctypes.data, st.size, now, idle,
+                                            out.ctypes.data, cap)
+        if rc < 0:
+            raise OSError(-rc, f"pptk_flow_table_expire failed ({rc})")
+        return out[:rc]
+
     def lookup_host(self, recs, subject=None):
         """pptk_flow_lookup_host over a NumPy array of records: (idx uint32,
         status uint8)."""
@@ -1204,6 +1292,58 @@ class FlowTable:
         if rc != 0:
             raise OSError(-rc, f"pptk_flow_lookup_host failed ({rc})")
         return idx[:n], st[:n]
+
+
+def _flow_stats(stats):
+    """A NumPy array of records.FLOW_STATS_DTYPE as the C calls need it: a
+    32-byte aligned one-dimensional array (the caller's own where it is one)."""
+    from .records import FLOW_STATS_DTYPE
+    if not (isinstance(stats, np.ndarray) and stats.dtype == FLOW_STATS_DTYPE and stats.ndim == 1
+            and stats.flags.c_contiguous):
+        raise ValueError("stats must be a 1-d contiguous array of records.FLOW_STATS_DTYPE")
+    if stats.ctypes.data & 31:
+        raise ValueError("stats must be 32-byte aligned (rx.flow_stats_array allocates one)")
+    return stats
+
+
+def flow_stats_array(count):
+    """A zeroed, 32-byte aligned array of `count` records.FLOW_STATS_DTYPE entries."""
+    from .records import FLOW_STATS_DTYPE
+    raw = np.zeros(count * 32 + 32, np.uint8)
+    skip = -raw.ctypes.data & 31
+    return raw[skip:skip + count * 32].view(FLOW_STATS_DTYPE)
+
+
+def flow_account_host(idx, stats, now, lens=None, fixed_len=0, unmatched=None, lib_path=None):
+    """pptk_flow_account_host, the CPU statement of flow_account_device, in
+    place: idx uint32, lens uint16 or None (then fixed_len), stats and
+    unmatched (one entry, optional) aligned arrays of records.FLOW_STATS_DTYPE
+    (flow_stats_array)."""
+    L = lib(lib_path)
+    if not hasattr(L, "pptk_flow_account_host"):
+        raise OSError(38, "this libpptkrx.so lacks pptk_flow_account_host")
+    i = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint16).reshape(-1)
+    if ln is not None and ln.size != i.size:
+        raise ValueError("flow_account_host: one length per index")
+    st = _flow_stats(stats)
+    um = None if unmatched is None else _flow_stats(unmatched)
+    rc = L.pptk_flow_account_host(i.ctypes.data, None if ln is None else ln.ctypes.data, fixed_len,
+                                  i.size, st.ctypes.data, st.size,
+                                  None if um is None else um.ctypes.data, now)
+    if rc != 0:
+        raise OSError(-rc, f"pptk_flow_account_host failed ({rc})")
+
+
+def flow_account_shape(lib_path=None):
+    """pptk_flow_account_shape: (segment_frames, lds_slots) of the library's
+    accounting kernel; lds_slots is 0 for a direct build."""
+    L = lib(lib_path)
+    if not hasattr(L, "pptk_flow_account_shape"):
+        raise OSError(38, "this libpptkrx.so lacks pptk_flow_account_shape")
+    s, k = ctypes.c_uint32(), ctypes.c_uint32()
+    L.pptk_flow_account_shape(ctypes.byref(s), ctypes.byref(k))
+    return s.value, k.value
 
 
 def ip_fragment_host(frame, mtu, out_cap, out_stride=0, lib_path=None):
