@@ -796,7 +796,9 @@ uint32_t pptk_tunnel_decap_host(const void *frame, uint32_t len, uint32_t *in_of
  * Last-seen stamps, per-flow counters and idle expiry are the next section,
  * "Flow state".
  *
- * Out of scope: inserts or deletes performed by a kernel, growth, a
+ * Out of scope: inserts or deletes performed by a kernel (the device only
+ * reports the new flows of a batch, "Flow learning" below; the host inserts),
+ * growth, a
  * direction-symmetric key (the caller inserts both directions),
  * pptk_rx_rec32 input (it lacks the IPv6 addresses), and locking. */
 struct pptk_flow_key {            /* 40 bytes: the tuple the flow hash covers */
@@ -930,6 +932,84 @@ int pptk_tx_rewrite_flow_device(struct pptk_rx_ctx *ctx, uint8_t *d_frames, cons
                                 const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
                                 uint64_t n, const struct pptk_rewrite *d_rw, uint64_t rw_count,
                                 const uint32_t *d_idx, uint8_t *d_status, void *stream);
+
+/* Flow learning: a device report of the new flows in a batch.  The host
+ * inserts flows and expires them, but the batches never leave device memory,
+ * so it does not see the frame of an unknown flow arrive: the lookup gives it
+ * PPTK_FLOW_NONE and status SUBJECT without HIT, and accounting adds it to
+ * `unmatched`.  The reference learns per packet -- ldp/ldpswitch.c:125-208
+ * port_put() adds an entry when its probe found none (:153-203) -- and a NAT
+ * or SYN proxy on hashtable/ does the same for a first packet.  Here a kernel
+ * turns the lookup's status bytes into a small array: one entry per new flow,
+ * free of duplicates, in frame order, ready for pptk_flow_table_insert_recs.
+ * No kernel inserts into the table or deletes from it: the device reports,
+ * the host decides policy and inserts, sync uploads.  The gateway loop is
+ *   rx -> pptk_flow_lookup_device -> pptk_flow_learn_device
+ *      -> download hdr + `written` entries -> policy
+ *      -> pptk_flow_table_insert_recs + stats_reset -> pptk_flow_table_sync.
+ *
+ * pptk_flow_learn_host is the CPU statement; the device call equals it byte
+ * for byte.  Walk i = 0 .. n - 1.  Frame i is a candidate when status[i] ==
+ * PPTK_FLOW_ST_SUBJECT exactly (a subject that did not hit); the status byte
+ * is trusted, the record's flags are not re-tested.  Candidates are numbered
+ * in index order and only the first max_candidates are considered; the rest
+ * count in hdr.candidates and nowhere else, which bounds work and scratch
+ * under a flood of new flows.  A map from flow_hash to the first considered
+ * frame L that carried it decides the rest: a considered frame whose hash is
+ * new is a leader; one whose hash is known and whose 37 key bytes (record
+ * bytes 8..43 plus proto) equal L's adds 1 to L's packet count; one whose hash
+ * is known but whose key differs is a leader of its own with count 1 and does
+ * not enter the map (a true 64-bit collision: a hash match alone is never a
+ * hit, as in the table).  The entries are the leaders in ascending frame
+ * index; entry k is written only for k < cap: new_recs[k] = the leader's
+ * record, all 64 bytes verbatim, first[k] = its frame index, packets[k] = its
+ * count.  Entries at and past `written` are untouched and nothing is written
+ * outside the arrays; hdr gets all four words.  Every value of flow_hash, 0
+ * and 2^64 - 1 included, is an ordinary hash.  n = 0 writes a zero header
+ * (where hdr is given) and launches no more than that; cap = 0 with null
+ * outputs is legal, the call then only counts; first and packets are
+ * nullable.
+ *
+ * -EINVAL: a null ctx (device call); null recs, status or hdr with n > 0;
+ * null new_recs with cap > 0; n >= 2^32; max_candidates 0 or above 2^30; recs
+ * or new_recs not 16-byte, hdr not 8-byte, first or packets not 4-byte
+ * aligned; and, on the device call with n > 0, a scratch that is null, not
+ * 256-byte aligned or smaller than pptk_flow_learn_scratch_bytes(n,
+ * max_candidates) (0 for n = 0 or arguments the call would reject).  status
+ * may have any alignment.  The host call returns -ENOMEM when its map cannot
+ * be allocated.
+ *
+ * The device call clears what it needs of the scratch itself, is
+ * asynchronous on `stream` (eight small launches ordered by the stream alone,
+ * no host synchronisation) and must not share a scratch with a call in
+ * flight on another stream.  Its cost follows n only through the status bytes
+ * (1 B per frame); records are read for considered candidates only.
+ * pptk_flow_learn_shape reports the built kernels: the frames of one
+ * workgroup of the counting passes (block_frames) and the block counts the
+ * scan's single workgroup takes per round (scan_width).  Results do not
+ * depend on it.
+ *
+ * Out of scope: a policy (which new flows to admit), inserts by a kernel,
+ * pptk_rx_rec32 input, and a report across batches (a flow learned from
+ * batch b is unknown to the lookup until the host has inserted and synced). */
+struct pptk_flow_learn_hdr {   /* 32 bytes, 8-byte aligned, in device memory */
+  uint64_t candidates;         /* frames with status == SUBJECT (no HIT)            */
+  uint64_t considered;         /* min(candidates, max_candidates)                   */
+  uint64_t flows;              /* report entries the considered frames give         */
+  uint64_t written;            /* min(flows, cap)                                   */
+};
+size_t pptk_flow_learn_scratch_bytes(uint64_t n, uint64_t max_candidates);
+int pptk_flow_learn_device(struct pptk_rx_ctx *ctx, const struct pptk_rx_rec *d_recs,
+                           const uint8_t *d_status, uint64_t n, uint64_t max_candidates,
+                           struct pptk_rx_rec *d_new_recs, uint32_t *d_first,
+                           uint32_t *d_packets, uint64_t cap,
+                           struct pptk_flow_learn_hdr *d_hdr,
+                           void *d_scratch, size_t scratch_bytes, void *stream);
+int pptk_flow_learn_host(const struct pptk_rx_rec *recs, const uint8_t *status, uint64_t n,
+                         uint64_t max_candidates, struct pptk_rx_rec *new_recs,
+                         uint32_t *first, uint32_t *packets, uint64_t cap,
+                         struct pptk_flow_learn_hdr *hdr);
+void pptk_flow_learn_shape(uint32_t *block_frames, uint32_t *scan_width);
 
 /* Tuning: force kernel variant `variant` (0 .. pptk_rx_variant_count()-1)
  * and/or memory-policy flags for every later batch of this context; -1

@@ -67,6 +67,10 @@ FLOW_ST_SUBJECT, FLOW_ST_HIT = 0x1, 0x2
 FLOW_STATS_DTYPE = np.dtype([("packets", "<u8"), ("bytes", "<u8"), ("last_seen", "<u8"),
                              ("reserved", "<u8")])
 assert FLOW_STATS_DTYPE.itemsize == 32
+# struct pptk_flow_learn_hdr (include/pptk_rx.h "Flow learning")
+FLOW_LEARN_HDR_DTYPE = np.dtype([("candidates", "<u8"), ("considered", "<u8"), ("flows", "<u8"),
+                                 ("written", "<u8")])
+assert FLOW_LEARN_HDR_DTYPE.itemsize == 32
 
 REC32_DTYPE = np.dtype([
     ("flow_hash", "<u8"),

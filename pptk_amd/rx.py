@@ -190,6 +190,8 @@ EXPORTS = ("pptk_rx_opts_default", "pptk_rx_ctx_create", "pptk_rx_ctx_destroy",
            "pptk_flow_lookup_device", "pptk_flow_lookup_host",
            "pptk_flow_account_device", "pptk_flow_account_host", "pptk_flow_stats_reset_device",
            "pptk_flow_account_shape", "pptk_flow_table_expire", "pptk_tx_rewrite_flow_device",
+           "pptk_flow_learn_scratch_bytes", "pptk_flow_learn_device", "pptk_flow_learn_host",
+           "pptk_flow_learn_shape",
            "pptk_rx_autotune", "pptk_rx_place_records",
            "pptk_rx_place_buffers", "pptk_rx_ring_alloc", "pptk_rx_ring_free",
            "pptk_rx_gather_alloc", "pptk_rx_gather_free",
@@ -367,6 +369,17 @@ def lib(path=None):
             L.pptk_tx_rewrite_flow_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, u64, vp,
                                                       vp, vp]
             L.pptk_tx_rewrite_flow_device.restype = ctypes.c_int
+        if hasattr(L, "pptk_flow_learn_device"):       # absent from older A/B builds
+            u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+            L.pptk_flow_learn_scratch_bytes.argtypes = [u64, u64]
+            L.pptk_flow_learn_scratch_bytes.restype = ctypes.c_size_t
+            L.pptk_flow_learn_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp,
+                                                 ctypes.c_size_t, vp]
+            L.pptk_flow_learn_device.restype = ctypes.c_int
+            L.pptk_flow_learn_host.argtypes = [vp, vp, u64, u64, vp, vp, vp, u64, vp]
+            L.pptk_flow_learn_host.restype = ctypes.c_int
+            L.pptk_flow_learn_shape.argtypes = [ctypes.POINTER(u32), ctypes.POINTER(u32)]
+            L.pptk_flow_learn_shape.restype = None
         if hasattr(L, "pptk_rx_permit_device"):        # absent from older A/B builds
             L.pptk_rx_permit_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
             L.pptk_rx_permit_scratch_bytes.restype = ctypes.c_size_t
@@ -981,6 +994,45 @@ class RxContext:
         if rc != 0:
             raise OSError(-rc, f"pptk_flow_stats_reset_device failed ({rc})")
 
+    def flow_learn_device(self, recs, status, max_candidates, cap, new_recs=None, first=None,
+                          packets=None, hdr=None, scratch=None, n=None, stream=None):
+        """pptk_flow_learn_device, asynchronous: the report of the new flows
+        among the n frames of recs (the uint8 CUDA tensor of 64-byte records)
+        by status (uint8 CUDA tensor, the status of flow_lookup_device).
+        Allocates what is not given -- new_recs (uint8, cap * 64 bytes), first
+        and packets (int32, cap entries; pass False for a null pointer), hdr
+        (int64, the four words of records.FLOW_LEARN_HDR_DTYPE) and the
+        scratch (uint8, flow_learn_scratch_bytes(n, max_candidates)) -- and
+        returns dict(hdr, new_recs, first, packets, scratch).  Download hdr,
+        then the first hdr.written entries of the arrays."""
+        import torch
+        if not hasattr(self._L, "pptk_flow_learn_device"):
+            raise OSError(38, "this libpptkrx.so lacks pptk_flow_learn_device")
+        dev = recs.device
+        n = recs.numel() * recs.element_size() // 64 if n is None else n
+        if new_recs is None and cap:
+            new_recs = torch.empty(cap * 64, dtype=torch.uint8, device=dev)
+        if first is None:
+            first = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        if packets is None:
+            packets = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        first = None if first is False else first
+        packets = None if packets is False else packets
+        if hdr is None:
+            hdr = torch.empty(4, dtype=torch.int64, device=dev)
+        need = self._L.pptk_flow_learn_scratch_bytes(n, max_candidates)
+        if scratch is None:
+            scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        rc = self._L.pptk_flow_learn_device(self._ctx, _dp(recs), _dp(status), n, max_candidates,
+                                            _dp(new_recs), _dp(first), _dp(packets), cap,
+                                            _dp(hdr), _dp(scratch),
+                                            scratch.numel() * scratch.element_size(),
+                                            ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise OSError(-rc, f"pptk_flow_learn_device failed ({rc})")
+        return dict(hdr=hdr, new_recs=new_recs, first=first, packets=packets, scratch=scratch)
+
     # ---- multi-GPU (RCCL) -------------------------------------------------
     def comm_create(self, nranks, rank, uid):
         """Join communicator `uid` (bytes from comm_uid()) as rank/nranks."""
@@ -1344,6 +1396,65 @@ def flow_account_shape(lib_path=None):
     s, k = ctypes.c_uint32(), ctypes.c_uint32()
     L.pptk_flow_account_shape(ctypes.byref(s), ctypes.byref(k))
     return s.value, k.value
+
+
+def _aligned_bytes(nbytes, align=64):
+    """A zeroed uint8 array of nbytes whose address is a multiple of align."""
+    raw = np.zeros(nbytes + align, np.uint8)
+    skip = -raw.ctypes.data & (align - 1)
+    return raw[skip:skip + nbytes]
+
+
+def flow_learn_host(recs, status, max_candidates, cap, lib_path=None):
+    """pptk_flow_learn_host, the CPU statement of flow_learn_device: recs a
+    NumPy array of records (records.REC_DTYPE, or its bytes), status the uint8
+    array of the lookup.  Returns (hdr, new_recs, first, packets): hdr one
+    records.FLOW_LEARN_HDR_DTYPE entry, the arrays cut to hdr.written entries
+    (records.REC_DTYPE, uint32, uint32)."""
+    from .records import FLOW_LEARN_HDR_DTYPE, REC_DTYPE
+    L = lib(lib_path)
+    if not hasattr(L, "pptk_flow_learn_host"):
+        raise OSError(38, "this libpptkrx.so lacks pptk_flow_learn_host")
+    r = np.ascontiguousarray(recs).view(np.uint8).reshape(-1)
+    n = r.size // 64
+    st = np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
+    if r.size != n * 64 or st.size != n:
+        raise ValueError("flow_learn_host: n 64-byte records and n status bytes")
+    if r.ctypes.data & 15:
+        a = _aligned_bytes(r.size)
+        a[:] = r
+        r = a
+    out = _aligned_bytes(max(cap, 1) * 64)
+    first = np.zeros(max(cap, 1), np.uint32)
+    packets = np.zeros(max(cap, 1), np.uint32)
+    hdr = np.zeros(1, FLOW_LEARN_HDR_DTYPE)
+    rc = L.pptk_flow_learn_host(r.ctypes.data, st.ctypes.data, n, max_candidates,
+                                out.ctypes.data if cap else None, first.ctypes.data,
+                                packets.ctypes.data, cap, hdr.ctypes.data)
+    if rc != 0:
+        raise OSError(-rc, f"pptk_flow_learn_host failed ({rc})")
+    w = int(hdr["written"][0])
+    return hdr[0], out[:w * 64].view(REC_DTYPE), first[:w], packets[:w]
+
+
+def flow_learn_scratch_bytes(n, max_candidates, lib_path=None):
+    """pptk_flow_learn_scratch_bytes: the device scratch a learn call over n
+    frames with this max_candidates needs (0 for n = 0)."""
+    L = lib(lib_path)
+    if not hasattr(L, "pptk_flow_learn_scratch_bytes"):
+        raise OSError(38, "this libpptkrx.so lacks pptk_flow_learn_scratch_bytes")
+    return L.pptk_flow_learn_scratch_bytes(n, max_candidates)
+
+
+def flow_learn_shape(lib_path=None):
+    """pptk_flow_learn_shape: (block_frames, scan_width) of the library's
+    learning kernels."""
+    L = lib(lib_path)
+    if not hasattr(L, "pptk_flow_learn_shape"):
+        raise OSError(38, "this libpptkrx.so lacks pptk_flow_learn_shape")
+    b, w = ctypes.c_uint32(), ctypes.c_uint32()
+    L.pptk_flow_learn_shape(ctypes.byref(b), ctypes.byref(w))
+    return b.value, w.value
 
 
 def ip_fragment_host(frame, mtu, out_cap, out_stride=0, lib_path=None):
