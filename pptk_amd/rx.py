@@ -126,7 +126,7 @@ class DeviceGather:
     no tensor over them is referenced."""
 
     def __init__(self, ctx, g):
-        import torch
+        torch = _torch()
         dev = torch.device("cuda", ctx.device)
         own = _GatherOwner(ctx._L, g)
         nb = g.nranks * g.per_rank * 8
@@ -146,7 +146,7 @@ class DeviceRing:
     tensor (nor a view of one) is referenced any more."""
 
     def __init__(self, ctx, ring):
-        import torch
+        torch = _torch()
         dev = torch.device("cuda", ctx.device)
         own = _RingOwner(ctx._L, ring)
         self.frames = torch.as_tensor(_DevMem(own, ring.d_frames, ring.frame_bytes + 64),
@@ -169,42 +169,125 @@ class LdpPacket(ctypes.Structure):
 assert ctypes.sizeof(LdpPacket) == 24
 assert ctypes.sizeof(RxOpts) == 40
 
-EXPORTS = ("pptk_rx_opts_default", "pptk_rx_ctx_create", "pptk_rx_ctx_destroy",
-           "pptk_rx_batch", "pptk_rx_batch32", "pptk_rx_batch_submit", "pptk_rx_batch_submit32",
-           "pptk_rx_batch_complete",
-           "pptk_rx_batch_pending", "pptk_rx_batch_device", "pptk_rx_bin_scratch_bytes",
-           "pptk_rx_bin_device", "pptk_rx_batch_device_mixed", "pptk_rx_version", "pptk_rx_set_tuning",
-           "pptk_rx_variant_count", "pptk_rx_last_variant", "pptk_rx_register_ring", "pptk_rx_unregister_ring",
-           "pptk_rx_permit_scratch_bytes", "pptk_rx_permit_device", "pptk_rx_permit_keys_device",
-           "pptk_rx_permit_status", "pptk_rx_tokens_refill_device", "pptk_tx_cksum_device", "pptk_tx_set_side_buffer",
-           "pptk_tx_rewrite_device",
-           "pptk_tcp_mss_clamp_device", "pptk_tcp_seq_translate_device",
-           "pptk_tcp_seq_translate_hdr", "pptk_ip_fragment_scratch_bytes",
-           "pptk_ip_fragment_device", "pptk_ip_fragment_host",
-           "pptk_tunnel_encap_device", "pptk_tunnel_decap_device",
-           "pptk_tunnel_encap_host", "pptk_tunnel_decap_host",
-           "pptk_flow_table_create", "pptk_flow_table_destroy", "pptk_flow_key_from_rec",
-           "pptk_flow_key_hash", "pptk_flow_table_insert", "pptk_flow_table_update",
-           "pptk_flow_table_delete", "pptk_flow_table_find", "pptk_flow_table_insert_recs",
-           "pptk_flow_table_clear", "pptk_flow_table_stats", "pptk_flow_table_sync",
-           "pptk_flow_lookup_device", "pptk_flow_lookup_host",
-           "pptk_flow_account_device", "pptk_flow_account_host", "pptk_flow_stats_reset_device",
-           "pptk_flow_account_shape", "pptk_flow_table_expire", "pptk_tx_rewrite_flow_device",
-           "pptk_flow_learn_scratch_bytes", "pptk_flow_learn_device", "pptk_flow_learn_host",
-           "pptk_flow_learn_shape",
-           "pptk_rx_autotune", "pptk_rx_place_records",
-           "pptk_rx_place_buffers", "pptk_rx_ring_alloc", "pptk_rx_ring_free",
-           "pptk_rx_gather_alloc", "pptk_rx_gather_free",
-           # multi-GPU (RCCL)
-           "pptk_rx_device_count", "pptk_rx_comm_uid", "pptk_rx_comm_create",
-           "pptk_rx_comm_create_all", "pptk_rx_comm_destroy", "pptk_rx_comm_info",
-           "pptk_rx_comm_abort", "pptk_rx_comm_sync",
-           "pptk_rx_shard_range", "pptk_rx_allgather_hash", "pptk_rx_stream_split",
-           "pptk_rx_stream_destroy", "pptk_rx_abi",
-           # kept per-packet APIs (ipcksum.h, hashseed.h)
-           "ip_cksum_feed", "ip_hdr_cksum_calc", "tcp_cksum_calc", "udp_cksum_calc",
-           "tcp6_cksum_calc", "udp6_cksum_calc", "hash_seed_init",
-           "tcp_parse_options", "tcp_find_sack_ts_headers", "tcp_find_sack_header")
+# Every C function this module binds: name -> (restype, argtypes), as its
+# prototype in include/*.h states (tests/test_capi.py compares the two).
+# Pointers to device memory, opaque handles and byte buffers are vp; lib()
+# sets both attributes on every function, so none is left with ctypes'
+# defaults (under which a uint64_t argument is cut to an int).
+P = ctypes.POINTER
+vp, ci, sz, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
+u16, u32, u64 = ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint64
+_batch, _cksum = (ci, (vp, vp, ci, vp)), (u16, (vp, u16, vp, u16))
+_SIGNATURES = {
+    # contexts, host batches, zero-copy rings
+    "pptk_rx_opts_default": (None, (P(RxOpts),)),
+    "pptk_rx_ctx_create": (ci, (P(vp), P(RxOpts))),
+    "pptk_rx_ctx_destroy": (None, (vp,)),
+    "pptk_rx_batch": _batch,
+    "pptk_rx_batch32": _batch,
+    "pptk_rx_batch_submit": _batch,
+    "pptk_rx_batch_submit32": _batch,
+    "pptk_rx_batch_complete": (ci, (vp,)),
+    "pptk_rx_batch_pending": (ci, (vp,)),
+    "pptk_rx_register_ring": (ci, (vp, vp, sz)),
+    "pptk_rx_unregister_ring": (ci, (vp, vp)),
+    # device batches and length binning
+    "pptk_rx_batch_device": (ci, (vp, P(RxDevBatch), vp)),
+    "pptk_rx_bin_scratch_bytes": (sz, (u64,)),
+    "pptk_rx_bin_device": (ci, (vp, vp, u64, vp, vp, vp)),
+    "pptk_rx_batch_device_mixed": (ci, (vp, P(RxDevBatch), vp, vp, vp)),
+    # rate limiter
+    "pptk_rx_permit_scratch_bytes": (sz, (u64, u32)),
+    "pptk_rx_permit_device": (ci, (vp, vp, vp, u64, ci, vp, vp, vp, vp, vp)),
+    "pptk_rx_permit_keys_device": (ci, (vp, vp, u64, ci, vp, vp, vp, vp, vp)),
+    "pptk_rx_permit_status": (ci, (vp, vp, vp)),
+    "pptk_rx_tokens_refill_device": (ci, (vp, vp, u32, u32, u32, u32, vp)),
+    # tx checksums and header edits
+    "pptk_tx_cksum_device": (ci, (vp, vp, vp, vp, u64, u32, u64, u32, vp)),
+    "pptk_tx_set_side_buffer": (ci, (vp, vp, u64)),
+    "pptk_tx_rewrite_device": (ci, (vp, vp, vp, vp, u64, u32, u64, vp, u64, vp, vp)),
+    "pptk_tcp_mss_clamp_device": (ci, (vp, vp, vp, vp, u64, u32, u64, u16, u32, vp, vp)),
+    "pptk_tcp_seq_translate_device": (ci, (vp, vp, vp, vp, u64, u32, u64, vp, u64, vp, vp, vp)),
+    "pptk_tcp_seq_translate_hdr": (u32, (vp, u32, vp)),
+    # IPv4 fragmentation
+    "pptk_ip_fragment_scratch_bytes": (sz, (u64,)),
+    "pptk_ip_fragment_device": (ci, (vp, vp, vp, vp, u64, u32, u64, u32, vp, u64, u64)
+                                + (vp,) * 8),
+    "pptk_ip_fragment_host": (ci, (vp, u32, u32, vp, u64, u32, vp, vp)),
+    # GRE tunnel
+    "pptk_tunnel_encap_device": (ci, (vp, vp, vp, vp, u64, u32, u64, vp, u64, vp, u32, vp, u64,
+                                      vp, vp, vp)),
+    "pptk_tunnel_decap_device": (ci, (vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp)),
+    "pptk_tunnel_encap_host": (u32, (vp, u32, vp, u32, vp, u64, vp)),
+    "pptk_tunnel_decap_host": (u32, (vp, u32, vp, vp)),
+    # flow table
+    "pptk_flow_table_create": (ci, (vp, u32, P(vp))),
+    "pptk_flow_table_destroy": (None, (vp,)),
+    "pptk_flow_key_from_rec": (None, (vp, vp)),
+    "pptk_flow_key_hash": (u64, (vp, vp)),
+    "pptk_flow_table_insert": (ci, (vp, vp, u64, u32)),
+    "pptk_flow_table_update": (ci, (vp, vp, u64, u32)),
+    "pptk_flow_table_delete": (ci, (vp, vp, u64)),
+    "pptk_flow_table_find": (ci, (vp, vp, u64, P(u32))),
+    "pptk_flow_table_insert_recs": (ci, (vp, vp, u64, vp, vp)),
+    "pptk_flow_table_clear": (None, (vp,)),
+    "pptk_flow_table_stats": (None, (vp, P(u32), P(u32), P(u32))),
+    "pptk_flow_table_sync": (ci, (vp, vp, P(u64))),
+    "pptk_flow_lookup_device": (ci, (vp, vp, vp, u64, vp, vp, vp, vp)),
+    "pptk_flow_lookup_host": (ci, (vp, vp, u64, vp, vp, vp)),
+    # flow state
+    "pptk_flow_account_device": (ci, (vp, vp, vp, u32, u64, vp, u64, vp, u64, vp)),
+    "pptk_flow_account_host": (ci, (vp, vp, u32, u64, vp, u64, vp, u64)),
+    "pptk_flow_stats_reset_device": (ci, (vp, vp, u64, vp, u64, u64, vp)),
+    "pptk_flow_account_shape": (None, (P(u32), P(u32))),
+    "pptk_flow_table_expire": (ci, (vp, vp, u64, u64, u64, vp, u32)),
+    "pptk_tx_rewrite_flow_device": (ci, (vp, vp, vp, vp, u64, u32, u64, vp, u64, vp, vp, vp)),
+    # flow learning
+    "pptk_flow_learn_scratch_bytes": (sz, (u64, u64)),
+    "pptk_flow_learn_device": (ci, (vp, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, sz, vp)),
+    "pptk_flow_learn_host": (ci, (vp, vp, u64, u64, vp, vp, vp, u64, vp)),
+    "pptk_flow_learn_shape": (None, (P(u32), P(u32))),
+    # tuning
+    "pptk_rx_set_tuning": (ci, (vp, ci, ci)),
+    "pptk_rx_variant_count": (ci, ()),
+    "pptk_rx_last_variant": (ci, (vp,)),
+    "pptk_rx_autotune": (ci, (vp, P(RxDevBatch), ci, vp)),
+    # multi-GPU (RCCL)
+    "pptk_rx_device_count": (ci, ()),
+    "pptk_rx_comm_uid": (ci, (vp,)),
+    "pptk_rx_comm_create": (ci, (vp, ci, ci, vp)),
+    "pptk_rx_comm_create_all": (ci, (P(vp), ci)),
+    "pptk_rx_comm_destroy": (ci, (vp,)),
+    "pptk_rx_comm_abort": (ci, (vp,)),
+    "pptk_rx_comm_sync": (ci, (vp, vp, u32)),
+    "pptk_rx_comm_info": (ci, (vp, P(ci), P(ci))),
+    "pptk_rx_shard_range": (None, (u64, ci, ci, P(u64), P(u64), P(u64))),
+    "pptk_rx_allgather_hash": (ci, (vp, vp, u64, vp, vp)),
+    "pptk_rx_stream_split": (ci, (vp, ci, P(vp), P(vp))),
+    "pptk_rx_stream_destroy": (ci, (vp,)),
+    # buffer placement, device rings, gather buffers
+    "pptk_rx_place_buffers": (ci, (vp, P(RxDevBatch), P(vp), ci, P(vp), ci, ci, P(ci), P(ci),
+                                   P(f32), vp)),
+    "pptk_rx_place_records": (ci, (vp, P(RxDevBatch), P(vp), ci, ci, P(ci), P(f32), vp)),
+    "pptk_rx_ring_alloc": (ci, (vp, P(RxRingSpec), P(RxRingC), vp)),
+    "pptk_rx_ring_free": (ci, (P(RxRingC),)),
+    "pptk_rx_gather_alloc": (ci, (vp, P(RxDevBatch), P(RxGatherSpec), P(RxGatherC), vp)),
+    "pptk_rx_gather_free": (ci, (P(RxGatherC),)),
+    "pptk_rx_version": (ctypes.c_char_p, ()),
+    "pptk_rx_abi": (ci, ()),
+    # kept per-packet APIs (ipcksum.h, hashseed.h, iphdr.h)
+    "ip_cksum_feed": (None, (P(u32), vp, sz)),
+    "ip_hdr_cksum_calc": (u16, (vp, u16)),
+    "tcp_cksum_calc": _cksum,
+    "udp_cksum_calc": _cksum,
+    "tcp6_cksum_calc": _cksum,
+    "udp6_cksum_calc": _cksum,
+    "hash_seed_init": (None, ()),
+    "tcp_parse_options": (None, (vp, vp)),
+    "tcp_find_sack_ts_headers": (None, (vp, vp)),
+    "tcp_find_sack_header": (vp, (vp, P(sz), P(ci))),
+}
+EXPORTS = tuple(_SIGNATURES)
 
 # Kernel variants, in the order of enum RxVariant (pptk_amd/csrc/rx_internal.h).
 VARIANTS = ("T4S1", "T4S2", "T16S2", "T16S6", "T32S3", "T64S2", "T16S7L", "T32S4L",
@@ -217,251 +300,81 @@ ABI = 6   # include/pptk_rx.h PPTK_RX_ABI
 
 def lib(path=None):
     """Load libpptkrx.so (or the A/B build at `path`) once; raise if it is
-    missing (no fallback)."""
+    missing (no fallback) or lacks a function of EXPORTS."""
     path = path or LIB_PATH
     if path not in _libs:
         if not os.path.exists(path):
             raise ImportError(f"{path} not built: run `make` or __graft_entry__.build()")
         L = ctypes.CDLL(path)
-        vp = ctypes.c_void_p
-        # the struct layouts below are PPTK_RX_ABI's (older A/B builds lack
-        # the symbol and are taken as they are)
-        if hasattr(L, "pptk_rx_abi") and L.pptk_rx_abi() != ABI:
+        missing = [f for f in _SIGNATURES if not hasattr(L, f)]
+        if missing:
+            raise ImportError(f"{path} lacks {', '.join(missing)}")
+        for f, (restype, argtypes) in _SIGNATURES.items():
+            fn = getattr(L, f)
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.pptk_rx_abi() != ABI:   # the struct layouts above are PPTK_RX_ABI's
             raise ImportError(f"{path}: struct layout revision {L.pptk_rx_abi()}, "
                               f"this binding expects {ABI}")
-        L.pptk_rx_opts_default.argtypes = [ctypes.POINTER(RxOpts)]
-        L.pptk_rx_opts_default.restype = None
-        L.pptk_rx_ctx_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(RxOpts)]
-        L.pptk_rx_ctx_create.restype = ctypes.c_int
-        L.pptk_rx_ctx_destroy.argtypes = [vp]
-        L.pptk_rx_ctx_destroy.restype = None
-        L.pptk_rx_batch.argtypes = [vp, vp, ctypes.c_int, vp]
-        L.pptk_rx_batch.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_batch32"):   # (absent from older A/B builds)
-            for f in ("pptk_rx_batch32", "pptk_rx_batch_submit32"):
-                getattr(L, f).argtypes = [vp, vp, ctypes.c_int, vp]
-                getattr(L, f).restype = ctypes.c_int
-        L.pptk_rx_batch_device.argtypes = [vp, ctypes.POINTER(RxDevBatch), vp]
-        L.pptk_rx_batch_device.restype = ctypes.c_int
-        L.pptk_rx_bin_scratch_bytes.argtypes = [ctypes.c_uint64]
-        L.pptk_rx_bin_scratch_bytes.restype = ctypes.c_size_t
-        L.pptk_rx_bin_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, vp]
-        L.pptk_rx_bin_device.restype = ctypes.c_int
-        if hasattr(L, "pptk_tx_cksum_device"):         # absent from older A/B builds
-            L.pptk_tx_cksum_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_uint32,
-                                               ctypes.c_uint64, ctypes.c_uint32, vp]
-            L.pptk_tx_cksum_device.restype = ctypes.c_int
-        if hasattr(L, "pptk_tx_set_side_buffer"):      # absent from older A/B builds
-            L.pptk_tx_set_side_buffer.argtypes = [vp, vp, ctypes.c_uint64]
-            L.pptk_tx_set_side_buffer.restype = ctypes.c_int
-        if hasattr(L, "pptk_tx_rewrite_device"):       # absent from older A/B builds
-            L.pptk_tx_rewrite_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_uint32,
-                                                 ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
-            L.pptk_tx_rewrite_device.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_autotune"):             # absent from older A/B builds
-            L.pptk_rx_autotune.argtypes = [vp, ctypes.POINTER(RxDevBatch), ctypes.c_int, vp]
-            L.pptk_rx_autotune.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_place_records"):        # absent from older A/B builds
-            L.pptk_rx_place_records.argtypes = [vp, ctypes.POINTER(RxDevBatch), ctypes.POINTER(vp),
-                                                ctypes.c_int, ctypes.c_int,
-                                                ctypes.POINTER(ctypes.c_int),
-                                                ctypes.POINTER(ctypes.c_float), vp]
-            L.pptk_rx_place_records.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_place_buffers"):        # absent from older A/B builds
-            L.pptk_rx_place_buffers.argtypes = [vp, ctypes.POINTER(RxDevBatch), ctypes.POINTER(vp),
-                                                ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int,
-                                                ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                                ctypes.POINTER(ctypes.c_int),
-                                                ctypes.POINTER(ctypes.c_float), vp]
-            L.pptk_rx_place_buffers.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_ring_alloc"):           # absent from older A/B builds
-            L.pptk_rx_ring_alloc.argtypes = [vp, ctypes.POINTER(RxRingSpec),
-                                             ctypes.POINTER(RxRingC), vp]
-            L.pptk_rx_ring_alloc.restype = ctypes.c_int
-            L.pptk_rx_ring_free.argtypes = [ctypes.POINTER(RxRingC)]
-            L.pptk_rx_ring_free.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_gather_alloc"):         # absent from older A/B builds
-            L.pptk_rx_gather_alloc.argtypes = [vp, ctypes.POINTER(RxDevBatch),
-                                               ctypes.POINTER(RxGatherSpec),
-                                               ctypes.POINTER(RxGatherC), vp]
-            L.pptk_rx_gather_alloc.restype = ctypes.c_int
-            L.pptk_rx_gather_free.argtypes = [ctypes.POINTER(RxGatherC)]
-            L.pptk_rx_gather_free.restype = ctypes.c_int
-        if hasattr(L, "pptk_tcp_mss_clamp_device"):    # absent from older A/B builds
-            L.pptk_tcp_mss_clamp_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
-                                                    ctypes.c_uint32, ctypes.c_uint64,
-                                                    ctypes.c_uint16, ctypes.c_uint32, vp, vp]
-            L.pptk_tcp_mss_clamp_device.restype = ctypes.c_int
-        if hasattr(L, "pptk_tcp_seq_translate_device"):   # absent from older A/B builds
-            L.pptk_tcp_seq_translate_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
-                                                        ctypes.c_uint32, ctypes.c_uint64, vp,
-                                                        ctypes.c_uint64, vp, vp, vp]
-            L.pptk_tcp_seq_translate_device.restype = ctypes.c_int
-            L.pptk_tcp_seq_translate_hdr.argtypes = [vp, ctypes.c_uint32, vp]
-            L.pptk_tcp_seq_translate_hdr.restype = ctypes.c_uint32
-        if hasattr(L, "pptk_ip_fragment_device"):      # absent from older A/B builds
-            L.pptk_ip_fragment_scratch_bytes.argtypes = [ctypes.c_uint64]
-            L.pptk_ip_fragment_scratch_bytes.restype = ctypes.c_size_t
-            L.pptk_ip_fragment_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
-                                                  ctypes.c_uint32, ctypes.c_uint64,
-                                                  ctypes.c_uint32, vp, ctypes.c_uint64,
-                                                  ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
-            L.pptk_ip_fragment_device.restype = ctypes.c_int
-            L.pptk_ip_fragment_host.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp,
-                                                ctypes.c_uint64, ctypes.c_uint32, vp, vp]
-            L.pptk_ip_fragment_host.restype = ctypes.c_int
-        if hasattr(L, "pptk_tunnel_encap_device"):     # absent from older A/B builds
-            L.pptk_tunnel_encap_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
-                                                   ctypes.c_uint32, ctypes.c_uint64, vp,
-                                                   ctypes.c_uint64, vp, ctypes.c_uint32, vp,
-                                                   ctypes.c_uint64, vp, vp, vp]
-            L.pptk_tunnel_encap_device.restype = ctypes.c_int
-            L.pptk_tunnel_decap_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64,
-                                                   ctypes.c_uint32, ctypes.c_uint64, vp, vp, vp,
-                                                   vp]
-            L.pptk_tunnel_decap_device.restype = ctypes.c_int
-            L.pptk_tunnel_encap_host.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp,
-                                                 ctypes.c_uint64, vp]
-            L.pptk_tunnel_encap_host.restype = ctypes.c_uint32
-            L.pptk_tunnel_decap_host.argtypes = [vp, ctypes.c_uint32, vp, vp]
-            L.pptk_tunnel_decap_host.restype = ctypes.c_uint32
-        if hasattr(L, "pptk_flow_table_create"):       # absent from older A/B builds
-            u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-            L.pptk_flow_table_create.argtypes = [vp, u32, ctypes.POINTER(vp)]
-            L.pptk_flow_table_create.restype = ctypes.c_int
-            L.pptk_flow_table_destroy.argtypes = [vp]
-            L.pptk_flow_table_destroy.restype = None
-            L.pptk_flow_key_from_rec.argtypes = [vp, vp]
-            L.pptk_flow_key_from_rec.restype = None
-            L.pptk_flow_key_hash.argtypes = [vp, vp]
-            L.pptk_flow_key_hash.restype = u64
-            for f in ("pptk_flow_table_insert", "pptk_flow_table_update"):
-                getattr(L, f).argtypes = [vp, vp, u64, u32]
-                getattr(L, f).restype = ctypes.c_int
-            L.pptk_flow_table_delete.argtypes = [vp, vp, u64]
-            L.pptk_flow_table_delete.restype = ctypes.c_int
-            L.pptk_flow_table_find.argtypes = [vp, vp, u64, ctypes.POINTER(u32)]
-            L.pptk_flow_table_find.restype = ctypes.c_int
-            L.pptk_flow_table_insert_recs.argtypes = [vp, vp, u64, vp, vp]
-            L.pptk_flow_table_insert_recs.restype = ctypes.c_int
-            L.pptk_flow_table_clear.argtypes = [vp]
-            L.pptk_flow_table_clear.restype = None
-            L.pptk_flow_table_stats.argtypes = [vp] + [ctypes.POINTER(u32)] * 3
-            L.pptk_flow_table_stats.restype = None
-            L.pptk_flow_table_sync.argtypes = [vp, vp, ctypes.POINTER(u64)]
-            L.pptk_flow_table_sync.restype = ctypes.c_int
-            L.pptk_flow_lookup_device.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
-            L.pptk_flow_lookup_device.restype = ctypes.c_int
-            L.pptk_flow_lookup_host.argtypes = [vp, vp, u64, vp, vp, vp]
-            L.pptk_flow_lookup_host.restype = ctypes.c_int
-        if hasattr(L, "pptk_flow_account_device"):     # absent from older A/B builds
-            u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-            L.pptk_flow_account_device.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, u64, vp]
-            L.pptk_flow_account_device.restype = ctypes.c_int
-            L.pptk_flow_account_host.argtypes = [vp, vp, u32, u64, vp, u64, vp, u64]
-            L.pptk_flow_account_host.restype = ctypes.c_int
-            L.pptk_flow_stats_reset_device.argtypes = [vp, vp, u64, vp, u64, u64, vp]
-            L.pptk_flow_stats_reset_device.restype = ctypes.c_int
-            L.pptk_flow_account_shape.argtypes = [ctypes.POINTER(u32), ctypes.POINTER(u32)]
-            L.pptk_flow_account_shape.restype = None
-            L.pptk_flow_table_expire.argtypes = [vp, vp, u64, u64, u64, vp, u32]
-            L.pptk_flow_table_expire.restype = ctypes.c_int
-            L.pptk_tx_rewrite_flow_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, u64, vp,
-                                                      vp, vp]
-            L.pptk_tx_rewrite_flow_device.restype = ctypes.c_int
-        if hasattr(L, "pptk_flow_learn_device"):       # absent from older A/B builds
-            u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-            L.pptk_flow_learn_scratch_bytes.argtypes = [u64, u64]
-            L.pptk_flow_learn_scratch_bytes.restype = ctypes.c_size_t
-            L.pptk_flow_learn_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp,
-                                                 ctypes.c_size_t, vp]
-            L.pptk_flow_learn_device.restype = ctypes.c_int
-            L.pptk_flow_learn_host.argtypes = [vp, vp, u64, u64, vp, vp, vp, u64, vp]
-            L.pptk_flow_learn_host.restype = ctypes.c_int
-            L.pptk_flow_learn_shape.argtypes = [ctypes.POINTER(u32), ctypes.POINTER(u32)]
-            L.pptk_flow_learn_shape.restype = None
-        if hasattr(L, "pptk_rx_permit_device"):        # absent from older A/B builds
-            L.pptk_rx_permit_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
-            L.pptk_rx_permit_scratch_bytes.restype = ctypes.c_size_t
-            L.pptk_rx_permit_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_int, vp,
-                                                vp, vp, vp, vp]
-            L.pptk_rx_permit_device.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_permit_keys_device"):   # absent from older A/B builds
-            L.pptk_rx_permit_keys_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_int, vp,
-                                                     vp, vp, vp, vp]
-            L.pptk_rx_permit_keys_device.restype = ctypes.c_int
-            L.pptk_rx_tokens_refill_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32,
-                                                       ctypes.c_uint32, ctypes.c_uint32, vp]
-            L.pptk_rx_tokens_refill_device.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_permit_status"):        # absent from older A/B builds
-            L.pptk_rx_permit_status.argtypes = [vp, vp, vp]
-            L.pptk_rx_permit_status.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_batch_device_mixed"):   # absent from older A/B builds
-            L.pptk_rx_batch_device_mixed.argtypes = [vp, ctypes.POINTER(RxDevBatch), vp, vp, vp]
-            L.pptk_rx_batch_device_mixed.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_allgather_hash"):       # absent from older A/B builds
-            L.pptk_rx_device_count.argtypes = []
-            L.pptk_rx_device_count.restype = ctypes.c_int
-            L.pptk_rx_comm_uid.argtypes = [vp]
-            L.pptk_rx_comm_uid.restype = ctypes.c_int
-            L.pptk_rx_comm_create.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
-            L.pptk_rx_comm_create.restype = ctypes.c_int
-            L.pptk_rx_comm_create_all.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
-            L.pptk_rx_comm_create_all.restype = ctypes.c_int
-            L.pptk_rx_comm_destroy.argtypes = [vp]
-            L.pptk_rx_comm_destroy.restype = ctypes.c_int
-            L.pptk_rx_comm_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int),
-                                            ctypes.POINTER(ctypes.c_int)]
-            L.pptk_rx_comm_info.restype = ctypes.c_int
-            u64p = ctypes.POINTER(ctypes.c_uint64)
-            L.pptk_rx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
-                                              u64p, u64p, u64p]
-            L.pptk_rx_shard_range.restype = None
-            L.pptk_rx_allgather_hash.argtypes = [vp, vp, ctypes.c_uint64, vp, vp]
-            L.pptk_rx_allgather_hash.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_comm_sync"):            # absent from older A/B builds
-            L.pptk_rx_comm_abort.argtypes = [vp]
-            L.pptk_rx_comm_abort.restype = ctypes.c_int
-            L.pptk_rx_comm_sync.argtypes = [vp, vp, ctypes.c_uint32]
-            L.pptk_rx_comm_sync.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_stream_split"):         # absent from older A/B builds
-            L.pptk_rx_stream_split.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp),
-                                               ctypes.POINTER(vp)]
-            L.pptk_rx_stream_split.restype = ctypes.c_int
-            L.pptk_rx_stream_destroy.argtypes = [vp]
-            L.pptk_rx_stream_destroy.restype = ctypes.c_int
-        L.pptk_rx_version.restype = ctypes.c_char_p
-        L.pptk_rx_set_tuning.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-        L.pptk_rx_set_tuning.restype = ctypes.c_int
-        L.pptk_rx_variant_count.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_last_variant"):   # (absent from older A/B builds)
-            L.pptk_rx_last_variant.argtypes = [vp]
-            L.pptk_rx_last_variant.restype = ctypes.c_int
-        if hasattr(L, "pptk_rx_batch_submit"):   # (absent from older A/B builds)
-            L.pptk_rx_batch_submit.argtypes = [vp, vp, ctypes.c_int, vp]
-            L.pptk_rx_batch_submit.restype = ctypes.c_int
-            L.pptk_rx_batch_complete.argtypes = [vp]
-            L.pptk_rx_batch_complete.restype = ctypes.c_int
-            L.pptk_rx_batch_pending.argtypes = [vp]
-            L.pptk_rx_batch_pending.restype = ctypes.c_int
-        L.pptk_rx_register_ring.argtypes = [vp, vp, ctypes.c_size_t]
-        L.pptk_rx_register_ring.restype = ctypes.c_int
-        L.pptk_rx_unregister_ring.argtypes = [vp, vp]
-        L.pptk_rx_unregister_ring.restype = ctypes.c_int
-        L.ip_hdr_cksum_calc.argtypes = [vp, ctypes.c_uint16]
-        L.ip_hdr_cksum_calc.restype = ctypes.c_uint16
-        for f in ("tcp_cksum_calc", "udp_cksum_calc", "tcp6_cksum_calc", "udp6_cksum_calc"):
-            getattr(L, f).argtypes = [vp, ctypes.c_uint16, vp, ctypes.c_uint16]
-            getattr(L, f).restype = ctypes.c_uint16
-        L.ip_cksum_feed.argtypes = [ctypes.POINTER(ctypes.c_uint32), vp, ctypes.c_size_t]
-        L.ip_cksum_feed.restype = None
         _libs[path] = L
     return _libs[path]
+
+
+def _torch():
+    """torch, imported at its first use: importing this module does not."""
+    import torch
+    return torch
 
 
 def _dp(t):
     """Device pointer of a torch tensor (or None)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _check(rc, name, counts=False):
+    """Raise the -errno return `rc` of C function `name` as OSError; with
+    `counts` a positive return is the call's result, otherwise an error too."""
+    if rc < 0 or (rc and not counts):
+        raise OSError(-rc, f"{name} failed ({rc})")
+    return rc
+
+
+def _stream(stream, device):
+    """The hipStream_t of `stream`, a torch stream or None = the current one
+    of `device`, as a C argument."""
+    if stream is None:
+        stream = _torch().cuda.current_stream(device)
+    return ctypes.c_void_p(stream.cuda_stream)
+
+
+def _empty(t, shape, dtype, device):
+    """`t`, or where it is None an uninitialised torch tensor of `shape` and
+    the dtype of that name on `device`."""
+    if t is None:
+        torch = _torch()
+        t = torch.empty(shape, dtype=getattr(torch, dtype), device=device)
+    return t
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _dev_batch(frames, n, off=None, lens=None, stride=0, fixed_len=0, max_len=0, perm=None,
+               recs=None, compact=False, hash_out=None, frag_out=None, key_out=None):
+    """struct pptk_rx_dev_batch over torch CUDA tensors (None = a null
+    pointer); recs goes into d_recs32 with compact, into d_recs without."""
+    r = _ptr(recs)
+    return RxDevBatch(_ptr(frames), _ptr(off), _ptr(lens), _ptr(perm), stride, fixed_len,
+                      max_len, n, None if compact else r, _ptr(hash_out),
+                      r if compact else None, _ptr(frag_out), _ptr(key_out))
+
+
+def _one_struct(x, arg, struct, nbytes):
+    """One C struct as a uint8 array, from a NumPy entry or its bytes."""
+    b = np.frombuffer(x.tobytes() if hasattr(x, "tobytes") else bytes(x), np.uint8)
+    if b.size != nbytes:
+        raise ValueError(f"{arg} must be one struct {struct} ({nbytes} bytes)")
+    return b
 
 
 class RxContext:
@@ -482,16 +395,14 @@ class RxContext:
             o.comm_timeout_ms = comm_timeout_ms
         self._ctx = ctypes.c_void_p()
         self._inflight = collections.deque()   # (pkts, out) of submitted host batches
-        rc = L.pptk_rx_ctx_create(ctypes.byref(self._ctx), ctypes.byref(o))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_ctx_create failed ({rc})")
+        _check(L.pptk_rx_ctx_create(ctypes.byref(self._ctx), ctypes.byref(o)),
+               "pptk_rx_ctx_create")
         self.device = device
 
     def set_tuning(self, variant=-1, flags=-1):
         """Force kernel variant / memory-policy flags (speed only; -1 = auto)."""
-        rc = self._L.pptk_rx_set_tuning(self._ctx, variant, flags)
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_set_tuning({variant}, {flags}) failed")
+        _check(self._L.pptk_rx_set_tuning(self._ctx, variant, flags),
+               f"pptk_rx_set_tuning({variant}, {flags})")
 
     def last_variant(self):
         """Kernel variant of the last device batch (-1: none yet)."""
@@ -518,22 +429,12 @@ class RxContext:
         32-byte struct pptk_rx_rec32 records (recs is (n, 32) bytes);
         frag_out: (n, 16) uint8 tensor of struct pptk_rx_frag side records;
         key_out: (n,) int32 tensor of dense rate-limiter keys (d_key)."""
-        import torch
-        rb = 32 if compact else 64
-        if recs is None:
-            recs = torch.empty((n, rb), dtype=torch.uint8, device=frames.device)
-        b = RxDevBatch(frames.data_ptr(), None if off is None else off.data_ptr(),
-                       None if lens is None else lens.data_ptr(),
-                       None if perm is None else perm.data_ptr(), stride, fixed_len,
-                       max_len, n, None if compact else recs.data_ptr(),
-                       None if hash_out is None else hash_out.data_ptr(),
-                       recs.data_ptr() if compact else None,
-                       None if frag_out is None else frag_out.data_ptr(),
-                       None if key_out is None else key_out.data_ptr())
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_rx_batch_device(self._ctx, ctypes.byref(b), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_batch_device failed ({rc})")
+        recs = _empty(recs, (n, 32 if compact else 64), "uint8", frames.device)
+        b = _dev_batch(frames, n, off, lens, stride, fixed_len, max_len, perm, recs, compact,
+                       hash_out, frag_out, key_out)
+        _check(self._L.pptk_rx_batch_device(self._ctx, ctypes.byref(b),
+                                            _stream(stream, frames.device)),
+               "pptk_rx_batch_device")
         return recs
 
     def autotune(self, frames, n, off=None, lens=None, stride=0, fixed_len=0, max_len=0,
@@ -541,19 +442,10 @@ class RxContext:
         """pptk_rx_autotune on this batch layout (synchronous): later device
         batches of the same shape use the fastest interchangeable kernel
         variant; returns its name (VARIANTS)."""
-        import torch
-        rb = 32 if compact else 64
-        if recs is None:
-            recs = torch.empty((n, rb), dtype=torch.uint8, device=frames.device)
-        b = RxDevBatch(frames.data_ptr(), None if off is None else off.data_ptr(),
-                       None if lens is None else lens.data_ptr(), None, stride, fixed_len,
-                       max_len, n, None if compact else recs.data_ptr(), None,
-                       recs.data_ptr() if compact else None)
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_rx_autotune(self._ctx, ctypes.byref(b), reps,
-                                      ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_autotune failed ({rc})")
+        recs = _empty(recs, (n, 32 if compact else 64), "uint8", frames.device)
+        b = _dev_batch(frames, n, off, lens, stride, fixed_len, max_len, None, recs, compact)
+        _check(self._L.pptk_rx_autotune(self._ctx, ctypes.byref(b), reps,
+                                        _stream(stream, frames.device)), "pptk_rx_autotune")
         return self.tuned_variant(frames, n, off, lens, stride, fixed_len, max_len, compact)
 
     def place_records(self, frames, n, cands, off=None, lens=None, stride=0, fixed_len=0,
@@ -561,19 +453,15 @@ class RxContext:
         """pptk_rx_place_records: run the batch into each candidate record
         buffer (torch uint8 CUDA tensors of n x 64 or n x 32 bytes) and
         return (index of the fastest, per-candidate median ms)."""
-        import torch
         arr = (ctypes.c_void_p * max(1, len(cands)))(*[t.data_ptr() for t in cands])
-        c0 = cands[0].data_ptr() if cands else None
-        b = RxDevBatch(frames.data_ptr(), None if off is None else off.data_ptr(),
-                       None if lens is None else lens.data_ptr(), None, stride, fixed_len,
-                       max_len, n, None if compact else c0, None, c0 if compact else None)
+        b = _dev_batch(frames, n, off, lens, stride, fixed_len, max_len, None,
+                       cands[0] if cands else None, compact)
         best = ctypes.c_int(-1)
         ms = (ctypes.c_float * max(1, len(cands)))()
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_rx_place_records(self._ctx, ctypes.byref(b), arr, len(cands), reps,
-                                           ctypes.byref(best), ms, ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_place_records failed ({rc})")
+        _check(self._L.pptk_rx_place_records(self._ctx, ctypes.byref(b), arr, len(cands), reps,
+                                             ctypes.byref(best), ms,
+                                             _stream(stream, frames.device)),
+               "pptk_rx_place_records")
         return best.value, [round(x, 4) for x in ms[:len(cands)]]
 
     def place_buffers(self, frame_cands, n, rec_cands, off=None, lens=None, stride=0,
@@ -581,24 +469,17 @@ class RxContext:
         """pptk_rx_place_buffers: the batch (the same bytes in every frame
         candidate) on every (frames, records) pair; returns (frame index,
         record index, median ms per pair, frames-major)."""
-        import torch
         nf, nr = len(frame_cands), len(rec_cands)
         fa = (ctypes.c_void_p * max(1, nf))(*[t.data_ptr() for t in frame_cands])
         ra = (ctypes.c_void_p * max(1, nr))(*[t.data_ptr() for t in rec_cands])
-        f0 = frame_cands[0].data_ptr() if nf else None
-        r0 = rec_cands[0].data_ptr() if nr else None
-        b = RxDevBatch(f0, None if off is None else off.data_ptr(),
-                       None if lens is None else lens.data_ptr(), None, stride, fixed_len,
-                       max_len, n, None if compact else r0, None, r0 if compact else None)
+        b = _dev_batch(frame_cands[0] if nf else None, n, off, lens, stride, fixed_len, max_len,
+                       None, rec_cands[0] if nr else None, compact)
         bf, br = ctypes.c_int(-1), ctypes.c_int(-1)
         ms = (ctypes.c_float * max(1, nf * nr))()
-        dev = frame_cands[0].device if nf else torch.device("cuda", self.device)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        rc = self._L.pptk_rx_place_buffers(self._ctx, ctypes.byref(b), fa, nf, ra, nr, reps,
-                                           ctypes.byref(bf), ctypes.byref(br), ms,
-                                           ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_place_buffers failed ({rc})")
+        dev = frame_cands[0].device if nf else _torch().device("cuda", self.device)
+        _check(self._L.pptk_rx_place_buffers(self._ctx, ctypes.byref(b), fa, nf, ra, nr, reps,
+                                             ctypes.byref(bf), ctypes.byref(br), ms,
+                                             _stream(stream, dev)), "pptk_rx_place_buffers")
         return bf.value, br.value, [round(x, 4) for x in ms[:nf * nr]]
 
     def ring_alloc(self, frame_bytes, nrec, rec_bytes=64, probe_len=0, frame_cands=0,
@@ -607,16 +488,12 @@ class RxContext:
         """pptk_rx_ring_alloc: placed device frame and record rings (a
         DeviceRing; its .report carries the probe).  probe_hash: the probe
         batches also write dense flow hashes (PPTK_RX_RING_PROBE_HASH)."""
-        import torch
         spec = RxRingSpec(frame_bytes, nrec, rec_bytes, probe_len, frame_cands, rec_cands, reps,
                           (RING_SETTLE if settle else 0) | (RING_PROBE_HASH if probe_hash else 0),
                           budget_bytes, 0)
         ring = RxRingC()
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        rc = self._L.pptk_rx_ring_alloc(self._ctx, ctypes.byref(spec), ctypes.byref(ring),
-                                        ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_ring_alloc failed ({rc})")
+        _check(self._L.pptk_rx_ring_alloc(self._ctx, ctypes.byref(spec), ctypes.byref(ring),
+                                          _stream(stream, self.device)), "pptk_rx_ring_alloc")
         return DeviceRing(self, ring)
 
     def gather_alloc(self, frames, n, per_rank, nranks, rank, off=None, lens=None, stride=0,
@@ -625,32 +502,23 @@ class RxContext:
         """pptk_rx_gather_alloc: this rank's two gather buffers, placed by a
         probe that runs the batch (frames/recs as for batch_device) with its
         hashes into each candidate; a DeviceGather."""
-        import torch
-        rb = 32 if compact else 64
-        if recs is None:
-            recs = torch.empty((n, rb), dtype=torch.uint8, device=frames.device)
-        b = RxDevBatch(frames.data_ptr(), None if off is None else off.data_ptr(),
-                       None if lens is None else lens.data_ptr(), None, stride, fixed_len,
-                       max_len, n, None if compact else recs.data_ptr(), None,
-                       recs.data_ptr() if compact else None)
+        recs = _empty(recs, (n, 32 if compact else 64), "uint8", frames.device)
+        b = _dev_batch(frames, n, off, lens, stride, fixed_len, max_len, None, recs, compact)
         spec = RxGatherSpec(per_rank, nranks, rank, cands, reps, RING_SETTLE if settle else 0, 0,
                             budget_bytes)
         g = RxGatherC()
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_rx_gather_alloc(self._ctx, ctypes.byref(b), ctypes.byref(spec),
-                                          ctypes.byref(g), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_gather_alloc failed ({rc})")
+        _check(self._L.pptk_rx_gather_alloc(self._ctx, ctypes.byref(b), ctypes.byref(spec),
+                                            ctypes.byref(g), _stream(stream, frames.device)),
+               "pptk_rx_gather_alloc")
         return DeviceGather(self, g)
 
     def tuned_variant(self, frames, n, off=None, lens=None, stride=0, fixed_len=0, max_len=0,
                       compact=False):
         """Name of the variant a device batch of this shape launches now
         (runs one batch of it: the variant is reported by the library)."""
-        import torch
         self.batch_device(frames, n, off=off, lens=lens, stride=stride, fixed_len=fixed_len,
                           max_len=max_len, compact=compact)
-        torch.cuda.synchronize(frames.device)
+        _torch().cuda.synchronize(frames.device)
         return VARIANTS[self._L.pptk_rx_last_variant(self._ctx)]
 
     def batch_device_mixed(self, frames, n, off, lens, recs=None, hash_out=None, max_len=0,
@@ -659,21 +527,14 @@ class RxContext:
         order, or device binning + one launch per length group when the batch
         mixes jumbo frames with shorter ones.  perm: optional device buffer
         that receives the processing order; scratch: optional preallocated."""
-        import torch
-        if recs is None:
-            recs = torch.empty((n, 64), dtype=torch.uint8, device=frames.device)
+        recs = _empty(recs, (n, 64), "uint8", frames.device)
         if scratch is None:
-            scratch = torch.empty(self._L.pptk_rx_bin_scratch_bytes(n), dtype=torch.uint8,
-                                  device=frames.device)
-        b = RxDevBatch(frames.data_ptr(), off.data_ptr(), lens.data_ptr(), None, 0, 0,
-                       max_len, n, recs.data_ptr(),
-                       None if hash_out is None else hash_out.data_ptr(), None,
-                       None if frag_out is None else frag_out.data_ptr())
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_rx_batch_device_mixed(self._ctx, ctypes.byref(b), _dp(perm),
-                                                _dp(scratch), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_batch_device_mixed failed ({rc})")
+            scratch = _empty(None, self._L.pptk_rx_bin_scratch_bytes(n), "uint8", frames.device)
+        b = _dev_batch(frames, n, off, lens, max_len=max_len, recs=recs, hash_out=hash_out,
+                       frag_out=frag_out)
+        _check(self._L.pptk_rx_batch_device_mixed(self._ctx, ctypes.byref(b), _dp(perm),
+                                                  _dp(scratch), _stream(stream, frames.device)),
+               "pptk_rx_batch_device_mixed")
         return recs
 
     def permit_device(self, recs, family, tokens, subject=None, compact=False, verdict=None,
@@ -681,76 +542,61 @@ class RxContext:
         """Batched ip(v6)_permitted over device records (torch uint8 (n, 64)
         or (n, 32) with compact); tokens: torch int32 (iphash_size) updated
         in place; returns the uint8 verdicts (1 permit, 0 deny, 2 n/a)."""
-        import torch
         n = recs.shape[0]
-        if verdict is None:
-            verdict = torch.empty(n, dtype=torch.uint8, device=recs.device)
+        verdict = _empty(verdict, n, "uint8", recs.device)
         if scratch is None:
-            scratch = torch.empty(self._L.pptk_rx_permit_scratch_bytes(n, tokens.numel()),
-                                  dtype=torch.uint8, device=recs.device)
-        s = stream if stream is not None else torch.cuda.current_stream(recs.device)
-        rc = self._L.pptk_rx_permit_device(self._ctx, None if compact else _dp(recs),
-                                           _dp(recs) if compact else None, n, family,
-                                           _dp(subject), _dp(tokens), _dp(verdict),
-                                           _dp(scratch), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_permit_device failed ({rc})")
+            scratch = _empty(None, self._L.pptk_rx_permit_scratch_bytes(n, tokens.numel()),
+                             "uint8", recs.device)
+        _check(self._L.pptk_rx_permit_device(self._ctx, None if compact else _dp(recs),
+                                             _dp(recs) if compact else None, n, family,
+                                             _dp(subject), _dp(tokens), _dp(verdict),
+                                             _dp(scratch), _stream(stream, recs.device)),
+               "pptk_rx_permit_device")
         return verdict
 
     def permit_keys_device(self, keys, family, tokens, subject=None, verdict=None, scratch=None,
                            stream=None):
         """pptk_rx_permit_keys_device: the rate limiter from the dense keys
         (torch int32 (n,)) a batch wrote through key_out."""
-        import torch
         n = keys.numel()
-        if verdict is None:
-            verdict = torch.empty(n, dtype=torch.uint8, device=keys.device)
+        verdict = _empty(verdict, n, "uint8", keys.device)
         if scratch is None:
-            scratch = torch.empty(self._L.pptk_rx_permit_scratch_bytes(n, tokens.numel()),
-                                  dtype=torch.uint8, device=keys.device)
-        s = stream if stream is not None else torch.cuda.current_stream(keys.device)
-        rc = self._L.pptk_rx_permit_keys_device(self._ctx, _dp(keys), n, family, _dp(subject),
-                                                _dp(tokens), _dp(verdict), _dp(scratch),
-                                                ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_permit_keys_device failed ({rc})")
+            scratch = _empty(None, self._L.pptk_rx_permit_scratch_bytes(n, tokens.numel()),
+                             "uint8", keys.device)
+        _check(self._L.pptk_rx_permit_keys_device(self._ctx, _dp(keys), n, family, _dp(subject),
+                                                  _dp(tokens), _dp(verdict), _dp(scratch),
+                                                  _stream(stream, keys.device)),
+               "pptk_rx_permit_keys_device")
         return verdict
 
     def permit_status(self, scratch, stream=None):
         """pptk_rx_permit_status: 0, or -ETIMEDOUT if a permit_keys_device
         call on `scratch` since the last query aborted (synchronises the
         stream)."""
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream(scratch.device)
-        return self._L.pptk_rx_permit_status(self._ctx, _dp(scratch), ctypes.c_void_p(s.cuda_stream))
+        return self._L.pptk_rx_permit_status(self._ctx, _dp(scratch),
+                                             _stream(stream, scratch.device))
 
     def tokens_refill_device(self, tokens, start, end, add, initial, stream=None):
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream(tokens.device)
-        rc = self._L.pptk_rx_tokens_refill_device(self._ctx, _dp(tokens), start, end, add,
-                                                  initial, ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_tokens_refill_device failed ({rc})")
+        _check(self._L.pptk_rx_tokens_refill_device(self._ctx, _dp(tokens), start, end, add,
+                                                    initial, _stream(stream, tokens.device)),
+               "pptk_rx_tokens_refill_device")
 
     def tx_cksum_device(self, frames, n, off=None, lens=None, stride=0, fixed_len=0, max_len=0,
                         stream=None):
         """Tx side: set the checksums of the frames in `frames` (torch uint8
         CUDA tensor) in place, asynchronously."""
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_tx_cksum_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
-                                          fixed_len, n, max_len, ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_tx_cksum_device failed ({rc})")
+        _check(self._L.pptk_tx_cksum_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
+                                            fixed_len, n, max_len,
+                                            _stream(stream, frames.device)),
+               "pptk_tx_cksum_device")
 
     def tx_set_side_buffer(self, buf):
         """pptk_tx_set_side_buffer: `buf` (a CUDA tensor of >= 8 bytes per
         frame, kept alive by the caller) as the two-pass tx side array, or
         None for the context's own."""
         nbytes = 0 if buf is None else buf.numel() * buf.element_size()
-        rc = self._L.pptk_tx_set_side_buffer(self._ctx, _dp(buf), nbytes // 8)
-        if rc != 0:
-            raise OSError(-rc, f"pptk_tx_set_side_buffer failed ({rc})")
+        _check(self._L.pptk_tx_set_side_buffer(self._ctx, _dp(buf), nbytes // 8),
+               "pptk_tx_set_side_buffer")
         self._tx_side = buf
 
     def tx_rewrite_device(self, frames, n, rw, off=None, lens=None, stride=0, fixed_len=0,
@@ -759,14 +605,11 @@ class RxContext:
         asynchronously.  rw: torch uint8 CUDA tensor of 1 or n struct
         pptk_rewrite entries (16 bytes each, records.REWRITE_DTYPE);
         status: optional torch uint8 CUDA tensor of n PPTK_RW_ST_* bytes."""
-        import torch
         count = rw.numel() // 16
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_tx_rewrite_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
-                                            fixed_len, n, _dp(rw), count, _dp(status),
-                                            ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_tx_rewrite_device failed ({rc})")
+        _check(self._L.pptk_tx_rewrite_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
+                                              fixed_len, n, _dp(rw), count, _dp(status),
+                                              _stream(stream, frames.device)),
+               "pptk_tx_rewrite_device")
 
     def tx_rewrite_flow_device(self, frames, n, rw, idx=None, off=None, lens=None, stride=0,
                                fixed_len=0, status=None, stream=None):
@@ -775,29 +618,23 @@ class RxContext:
         n entries, the idx of flow_lookup_device; an index at or past the
         table, -1 = FLOW_NONE among them, leaves the frame alone with status
         records.RW_ST_NOFLOW).  idx=None is tx_rewrite_device itself."""
-        import torch
-        if not hasattr(self._L, "pptk_tx_rewrite_flow_device"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_tx_rewrite_flow_device")
         count = rw.numel() * rw.element_size() // 16
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_tx_rewrite_flow_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
-                                                 stride, fixed_len, n, _dp(rw), count, _dp(idx),
-                                                 _dp(status), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_tx_rewrite_flow_device failed ({rc})")
+        _check(self._L.pptk_tx_rewrite_flow_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
+                                                   stride, fixed_len, n, _dp(rw), count,
+                                                   _dp(idx), _dp(status),
+                                                   _stream(stream, frames.device)),
+               "pptk_tx_rewrite_flow_device")
 
     def mss_clamp_device(self, frames, n, mss, syn_only=False, off=None, lens=None, stride=0,
                          fixed_len=0, status=None, stream=None):
         """TCP MSS clamping with incremental checksum update, in place and
         asynchronously; status: optional torch uint8 CUDA tensor of n
         PPTK_MSS_ST_* bytes."""
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_tcp_mss_clamp_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
-                                               stride, fixed_len, n, mss, 1 if syn_only else 0,
-                                               _dp(status), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_tcp_mss_clamp_device failed ({rc})")
+        _check(self._L.pptk_tcp_mss_clamp_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
+                                                 stride, fixed_len, n, mss,
+                                                 1 if syn_only else 0, _dp(status),
+                                                 _stream(stream, frames.device)),
+               "pptk_tcp_mss_clamp_device")
 
     def seq_translate_device(self, frames, n, xl, idx=None, off=None, lens=None, stride=0,
                              fixed_len=0, status=None, stream=None):
@@ -807,17 +644,12 @@ class RxContext:
         of them, or a flow table indexed by idx (torch int32 CUDA tensor of n
         entries, -1 = 0xffffffff = no flow); status: optional torch uint8
         CUDA tensor of n PPTK_SEQ_ST_* bytes."""
-        import torch
-        if not hasattr(self._L, "pptk_tcp_seq_translate_device"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_tcp_seq_translate_device")
         count = xl.numel() * xl.element_size() // 24
-        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        rc = self._L.pptk_tcp_seq_translate_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
-                                                   stride, fixed_len, n, _dp(xl), count,
-                                                   _dp(idx), _dp(status),
-                                                   ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_tcp_seq_translate_device failed ({rc})")
+        _check(self._L.pptk_tcp_seq_translate_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
+                                                     stride, fixed_len, n, _dp(xl), count,
+                                                     _dp(idx), _dp(status),
+                                                     _stream(stream, frames.device)),
+               "pptk_tcp_seq_translate_device")
 
     def ip_fragment_device(self, frames, n, mtu, out_cap, off=None, lens=None, stride=0,
                            fixed_len=0, out=None, out_stride=0, out_len=None, out_src=None,
@@ -830,34 +662,23 @@ class RxContext:
         scratch -- and returns them as a dict.  Rows [0, totals[1]) of out
         hold the fragments; the views are the C arrays' bits (out_len is
         uint16 in C)."""
-        import torch
         dev = frames.device
         out_stride = out_stride or (18 + mtu + 15) & ~15
-        if out is None:
-            out = torch.empty((out_cap, out_stride), dtype=torch.uint8, device=dev)
-        if out_len is None:
-            out_len = torch.empty(out_cap, dtype=torch.int16, device=dev)
-        if out_src is None:
-            out_src = torch.empty(out_cap, dtype=torch.int32, device=dev)
-        if first is None:
-            first = torch.empty(n, dtype=torch.int32, device=dev)
-        if count is None:
-            count = torch.empty(n, dtype=torch.int32, device=dev)
-        if status is None:
-            status = torch.empty(n, dtype=torch.uint8, device=dev)
-        if totals is None:
-            totals = torch.empty(2, dtype=torch.int64, device=dev)
+        out = _empty(out, (out_cap, out_stride), "uint8", dev)
+        out_len = _empty(out_len, out_cap, "int16", dev)
+        out_src = _empty(out_src, out_cap, "int32", dev)
+        first = _empty(first, n, "int32", dev)
+        count = _empty(count, n, "int32", dev)
+        status = _empty(status, n, "uint8", dev)
+        totals = _empty(totals, 2, "int64", dev)
         if scratch is None:
-            scratch = torch.empty(self._L.pptk_ip_fragment_scratch_bytes(n), dtype=torch.uint8,
-                                  device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        rc = self._L.pptk_ip_fragment_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
-                                             fixed_len, n, mtu, _dp(out), out_stride, out_cap,
-                                             _dp(out_len), _dp(out_src), _dp(first), _dp(count),
-                                             _dp(status), _dp(totals), _dp(scratch),
-                                             ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_ip_fragment_device failed ({rc})")
+            scratch = _empty(None, self._L.pptk_ip_fragment_scratch_bytes(n), "uint8", dev)
+        _check(self._L.pptk_ip_fragment_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
+                                               stride, fixed_len, n, mtu, _dp(out), out_stride,
+                                               out_cap, _dp(out_len), _dp(out_src), _dp(first),
+                                               _dp(count), _dp(status), _dp(totals),
+                                               _dp(scratch), _stream(stream, dev)),
+               "pptk_ip_fragment_device")
         return dict(out=out, out_stride=out_stride, out_len=out_len, out_src=out_src, first=first,
                     count=count, status=status, totals=totals, scratch=scratch)
 
@@ -874,34 +695,26 @@ class RxContext:
         ((n, out_stride) uint8; out_stride = round_up(38 + fixed_len, 16)
         unless given, and required with lens), out_len (int16), status (uint8) --
         and returns them as a dict; out_len holds the C array's uint16 bits."""
-        import torch
         from .records import TUN_DF, TUN_HDR_LEN, TUN_ID_SEQ, TUNNEL_DTYPE
-        if not hasattr(self._L, "pptk_tunnel_encap_device"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_tunnel_encap_device")
         dev = frames.device
         if isinstance(tun, np.ndarray):
             t = np.ascontiguousarray(tun, dtype=TUNNEL_DTYPE).reshape(-1)
             if np.any(t["reserved"]) or np.any(t["flags"] & ~np.uint32(TUN_DF | TUN_ID_SEQ)):
                 raise OSError(22, "struct pptk_tunnel: reserved must be 0, flags DF | ID_SEQ")
-            tun = torch.from_numpy(t.view(np.uint8).copy()).to(dev)
+            tun = _torch().from_numpy(t.view(np.uint8).copy()).to(dev)
         count = tun.numel() * tun.element_size() // 32
         if not out_stride:
             if lens is not None:   # (the lengths are device data: n x 64 KB would be the only safe guess)
                 raise ValueError("tunnel_encap_device: out_stride is required with lens")
             out_stride = (TUN_HDR_LEN + fixed_len + 15) & ~15
-        if out is None:
-            out = torch.empty((n, out_stride), dtype=torch.uint8, device=dev)
-        if out_len is None:
-            out_len = torch.empty(n, dtype=torch.int16, device=dev)
-        if status is None:
-            status = torch.empty(n, dtype=torch.uint8, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        rc = self._L.pptk_tunnel_encap_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
-                                              fixed_len, n, _dp(tun), count, _dp(idx), id_base,
-                                              _dp(out), out_stride, _dp(out_len), _dp(status),
-                                              ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_tunnel_encap_device failed ({rc})")
+        out = _empty(out, (n, out_stride), "uint8", dev)
+        out_len = _empty(out_len, n, "int16", dev)
+        status = _empty(status, n, "uint8", dev)
+        _check(self._L.pptk_tunnel_encap_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
+                                                stride, fixed_len, n, _dp(tun), count, _dp(idx),
+                                                id_base, _dp(out), out_stride, _dp(out_len),
+                                                _dp(status), _stream(stream, dev)),
+               "pptk_tunnel_encap_device")
         return dict(out=out, out_stride=out_stride, out_len=out_len, status=status, tun=tun)
 
     def tunnel_decap_device(self, frames, n, off=None, lens=None, stride=0, fixed_len=0,
@@ -911,22 +724,14 @@ class RxContext:
         Allocates what is not given -- in_off (int64), in_len (int16), status
         (uint8) -- and returns them as a dict; in_off / in_len go into
         batch_device as off / lens."""
-        import torch
-        if not hasattr(self._L, "pptk_tunnel_decap_device"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_tunnel_decap_device")
         dev = frames.device
-        if in_off is None:
-            in_off = torch.empty(n, dtype=torch.int64, device=dev)
-        if in_len is None:
-            in_len = torch.empty(n, dtype=torch.int16, device=dev)
-        if status is None:
-            status = torch.empty(n, dtype=torch.uint8, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        rc = self._L.pptk_tunnel_decap_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
-                                              fixed_len, n, _dp(in_off), _dp(in_len), _dp(status),
-                                              ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_tunnel_decap_device failed ({rc})")
+        in_off = _empty(in_off, n, "int64", dev)
+        in_len = _empty(in_len, n, "int16", dev)
+        status = _empty(status, n, "uint8", dev)
+        _check(self._L.pptk_tunnel_decap_device(self._ctx, _dp(frames), _dp(off), _dp(lens),
+                                                stride, fixed_len, n, _dp(in_off), _dp(in_len),
+                                                _dp(status), _stream(stream, dev)),
+               "pptk_tunnel_decap_device")
         return dict(in_off=in_off, in_len=in_len, status=status)
 
     def flow_table(self, slots):
@@ -941,21 +746,13 @@ class RxContext:
         int32 (the C array's uint32 bits, -1 = FLOW_NONE = no flow), ready to
         be the idx= of seq_translate_device / tunnel_encap_device; status
         uint8 FLOW_ST_* bits."""
-        import torch
-        if not hasattr(self._L, "pptk_flow_lookup_device"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_flow_lookup_device")
         dev = recs.device
         n = recs.numel() * recs.element_size() // 64
-        if idx is None:
-            idx = torch.empty(n, dtype=torch.int32, device=dev)
-        if status is None:
-            status = torch.empty(n, dtype=torch.uint8, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        rc = self._L.pptk_flow_lookup_device(self._ctx, table._t, _dp(recs), n, _dp(subject),
-                                             _dp(idx), _dp(status),
-                                             ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_lookup_device failed ({rc})")
+        idx = _empty(idx, n, "int32", dev)
+        status = _empty(status, n, "uint8", dev)
+        _check(self._L.pptk_flow_lookup_device(self._ctx, table._t, _dp(recs), n, _dp(subject),
+                                               _dp(idx), _dp(status), _stream(stream, dev)),
+               "pptk_flow_lookup_device")
         return idx, status
 
     def flow_account_device(self, idx, stats, now, lens=None, fixed_len=0, unmatched=None,
@@ -968,31 +765,21 @@ class RxContext:
         fixed_len, and stamps the entries with `now`.  Frames whose index is
         at or past the array go to unmatched (one entry, optional).  The
         tensors accumulate: the caller zeroes them once."""
-        import torch
-        if not hasattr(self._L, "pptk_flow_account_device"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_flow_account_device")
         n = idx.numel() if n is None else n
         count = stats.numel() * stats.element_size() // 32
-        s = stream if stream is not None else torch.cuda.current_stream(stats.device)
-        rc = self._L.pptk_flow_account_device(self._ctx, _dp(idx), _dp(lens), fixed_len, n,
-                                              _dp(stats), count, _dp(unmatched), now,
-                                              ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_account_device failed ({rc})")
+        _check(self._L.pptk_flow_account_device(self._ctx, _dp(idx), _dp(lens), fixed_len, n,
+                                                _dp(stats), count, _dp(unmatched), now,
+                                                _stream(stream, stats.device)),
+               "pptk_flow_account_device")
 
     def flow_stats_reset_device(self, stats, values, now, stream=None):
         """pptk_flow_stats_reset_device, asynchronous: stats[v] = {0, 0, now}
         for every v of values (torch int32 CUDA tensor) inside the array."""
-        import torch
-        if not hasattr(self._L, "pptk_flow_stats_reset_device"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_flow_stats_reset_device")
         count = stats.numel() * stats.element_size() // 32
-        s = stream if stream is not None else torch.cuda.current_stream(stats.device)
-        rc = self._L.pptk_flow_stats_reset_device(self._ctx, _dp(stats), count, _dp(values),
-                                                  values.numel(), now,
-                                                  ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_stats_reset_device failed ({rc})")
+        _check(self._L.pptk_flow_stats_reset_device(self._ctx, _dp(stats), count, _dp(values),
+                                                    values.numel(), now,
+                                                    _stream(stream, stats.device)),
+               "pptk_flow_stats_reset_device")
 
     def flow_learn_device(self, recs, status, max_candidates, cap, new_recs=None, first=None,
                           packets=None, hdr=None, scratch=None, n=None, stream=None):
@@ -1005,59 +792,40 @@ class RxContext:
         scratch (uint8, flow_learn_scratch_bytes(n, max_candidates)) -- and
         returns dict(hdr, new_recs, first, packets, scratch).  Download hdr,
         then the first hdr.written entries of the arrays."""
-        import torch
-        if not hasattr(self._L, "pptk_flow_learn_device"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_flow_learn_device")
         dev = recs.device
         n = recs.numel() * recs.element_size() // 64 if n is None else n
-        if new_recs is None and cap:
-            new_recs = torch.empty(cap * 64, dtype=torch.uint8, device=dev)
-        if first is None:
-            first = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        if packets is None:
-            packets = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        first = None if first is False else first
-        packets = None if packets is False else packets
-        if hdr is None:
-            hdr = torch.empty(4, dtype=torch.int64, device=dev)
+        if cap:
+            new_recs = _empty(new_recs, cap * 64, "uint8", dev)
+        first = None if first is False else _empty(first, max(cap, 1), "int32", dev)
+        packets = None if packets is False else _empty(packets, max(cap, 1), "int32", dev)
+        hdr = _empty(hdr, 4, "int64", dev)
         need = self._L.pptk_flow_learn_scratch_bytes(n, max_candidates)
-        if scratch is None:
-            scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        rc = self._L.pptk_flow_learn_device(self._ctx, _dp(recs), _dp(status), n, max_candidates,
-                                            _dp(new_recs), _dp(first), _dp(packets), cap,
-                                            _dp(hdr), _dp(scratch),
-                                            scratch.numel() * scratch.element_size(),
-                                            ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_learn_device failed ({rc})")
+        scratch = _empty(scratch, max(need, 256), "uint8", dev)
+        _check(self._L.pptk_flow_learn_device(self._ctx, _dp(recs), _dp(status), n,
+                                              max_candidates, _dp(new_recs), _dp(first),
+                                              _dp(packets), cap, _dp(hdr), _dp(scratch),
+                                              scratch.numel() * scratch.element_size(),
+                                              _stream(stream, dev)), "pptk_flow_learn_device")
         return dict(hdr=hdr, new_recs=new_recs, first=first, packets=packets, scratch=scratch)
 
     # ---- multi-GPU (RCCL) -------------------------------------------------
     def comm_create(self, nranks, rank, uid):
         """Join communicator `uid` (bytes from comm_uid()) as rank/nranks."""
-        rc = self._L.pptk_rx_comm_create(self._ctx, nranks, rank, bytes(uid))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_comm_create({nranks}, {rank}) failed ({rc})")
+        _check(self._L.pptk_rx_comm_create(self._ctx, nranks, rank, bytes(uid)),
+               f"pptk_rx_comm_create({nranks}, {rank})")
 
     def comm_destroy(self):
-        rc = self._L.pptk_rx_comm_destroy(self._ctx)
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_comm_destroy failed ({rc})")
+        _check(self._L.pptk_rx_comm_destroy(self._ctx), "pptk_rx_comm_destroy")
 
     def comm_abort(self):
         """pptk_rx_comm_abort: cancel the communicator (any thread)."""
-        rc = self._L.pptk_rx_comm_abort(self._ctx)
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_comm_abort failed ({rc})")
+        _check(self._L.pptk_rx_comm_abort(self._ctx), "pptk_rx_comm_abort")
 
     def comm_sync(self, stream=None, timeout_ms=0):
         """pptk_rx_comm_sync: bounded wait for `stream` (torch stream, None =
         current) with RCCL error checks; returns 0 or the negative errno
         (-ETIMEDOUT / -EIO / -ECANCELED: the communicator is then dead)."""
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        return self._L.pptk_rx_comm_sync(self._ctx, ctypes.c_void_p(s.cuda_stream), timeout_ms)
+        return self._L.pptk_rx_comm_sync(self._ctx, _stream(stream, self.device), timeout_ms)
 
     def comm_info(self):
         """(nranks, rank) of the context's communicator, or None."""
@@ -1068,12 +836,9 @@ class RxContext:
     def allgather_hash(self, d_hash, n, d_out, stream=None):
         """pptk_rx_allgather_hash: n u64 per rank from d_hash into d_out
         (torch int64 CUDA tensors), asynchronous on `stream`."""
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream(d_out.device)
-        rc = self._L.pptk_rx_allgather_hash(self._ctx, _dp(d_hash), n, _dp(d_out),
-                                            ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_allgather_hash failed ({rc})")
+        _check(self._L.pptk_rx_allgather_hash(self._ctx, _dp(d_hash), n, _dp(d_out),
+                                              _stream(stream, d_out.device)),
+               "pptk_rx_allgather_hash")
 
     def stream_split(self, coll_cus):
         """pptk_rx_stream_split: (rx stream, collective stream) as torch
@@ -1082,11 +847,10 @@ class RxContext:
         context sizes its grids for the rest until stream_join().  Call it
         before creating the communicator (its channel cap follows coll_cus).
         The HIP streams belong to the context and are destroyed with it."""
-        import torch
+        torch = _torch()
         a, b = ctypes.c_void_p(), ctypes.c_void_p()
-        rc = self._L.pptk_rx_stream_split(self._ctx, coll_cus, ctypes.byref(a), ctypes.byref(b))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_stream_split({coll_cus}) failed ({rc})")
+        _check(self._L.pptk_rx_stream_split(self._ctx, coll_cus, ctypes.byref(a),
+                                            ctypes.byref(b)), f"pptk_rx_stream_split({coll_cus})")
         dev = torch.device("cuda", self.device)
         return (torch.cuda.ExternalStream(a.value, device=dev),
                 torch.cuda.ExternalStream(b.value, device=dev))
@@ -1094,33 +858,24 @@ class RxContext:
     def stream_join(self):
         """Undo stream_split: the whole chip for this context's grids again
         (the split's streams stay the context's until close())."""
-        if not hasattr(self._L, "pptk_rx_stream_split"):
-            return
         self._L.pptk_rx_stream_split(self._ctx, 0, None, None)
 
     def bin_device(self, lens, n, stream=None):
         """Stable permutation of 0..n-1 by length class (torch uint32 tensor)."""
-        import torch
-        perm = torch.empty(n, dtype=torch.int32, device=lens.device)
-        scratch = torch.empty(self._L.pptk_rx_bin_scratch_bytes(n), dtype=torch.uint8,
-                              device=lens.device)
-        s = stream if stream is not None else torch.cuda.current_stream(lens.device)
-        rc = self._L.pptk_rx_bin_device(self._ctx, _dp(lens), n, _dp(perm), _dp(scratch),
-                                      ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_bin_device failed ({rc})")
+        perm = _empty(None, n, "int32", lens.device)
+        scratch = _empty(None, self._L.pptk_rx_bin_scratch_bytes(n), "uint8", lens.device)
+        _check(self._L.pptk_rx_bin_device(self._ctx, _dp(lens), n, _dp(perm), _dp(scratch),
+                                          _stream(stream, lens.device)), "pptk_rx_bin_device")
         return perm
 
     def register_ring(self, buf):
         """Register numpy buffer `buf` as a zero-copy rx ring."""
-        rc = self._L.pptk_rx_register_ring(self._ctx, ctypes.c_void_p(buf.ctypes.data), buf.nbytes)
-        if rc != 0:
-            raise OSError(-rc, "pptk_rx_register_ring failed")
+        _check(self._L.pptk_rx_register_ring(self._ctx, ctypes.c_void_p(buf.ctypes.data),
+                                             buf.nbytes), "pptk_rx_register_ring")
 
     def unregister_ring(self, buf):
-        rc = self._L.pptk_rx_unregister_ring(self._ctx, ctypes.c_void_p(buf.ctypes.data))
-        if rc != 0:
-            raise OSError(-rc, "pptk_rx_unregister_ring failed")
+        _check(self._L.pptk_rx_unregister_ring(self._ctx, ctypes.c_void_p(buf.ctypes.data)),
+               "pptk_rx_unregister_ring")
 
     def batch_host(self, pkts, out=None, compact=False):
         """pptk_rx_batch (compact: pptk_rx_batch32, 32-byte records) over a
@@ -1135,9 +890,8 @@ class RxContext:
         else:
             recs = np.zeros(n, dtype=dt)
         fn = self._L.pptk_rx_batch32 if compact else self._L.pptk_rx_batch
-        rc = fn(self._ctx, ctypes.cast(pkts, ctypes.c_void_p), n, ctypes.c_void_p(recs.ctypes.data))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_batch{'32' if compact else ''} failed ({rc})")
+        _check(fn(self._ctx, ctypes.cast(pkts, ctypes.c_void_p), n,
+                  ctypes.c_void_p(recs.ctypes.data)), fn.__name__)
         return recs
 
     def submit_host(self, pkts, out):
@@ -1151,9 +905,8 @@ class RxContext:
         compact = out.dtype == REC32_DTYPE
         assert (compact or out.dtype == REC_DTYPE) and out.shape == (n,) and out.flags["C_CONTIGUOUS"]
         fn = self._L.pptk_rx_batch_submit32 if compact else self._L.pptk_rx_batch_submit
-        rc = fn(self._ctx, ctypes.cast(pkts, ctypes.c_void_p), n, ctypes.c_void_p(out.ctypes.data))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_rx_batch_submit failed ({rc})")
+        _check(fn(self._ctx, ctypes.cast(pkts, ctypes.c_void_p), n,
+                  ctypes.c_void_p(out.ctypes.data)), fn.__name__)
         # the library holds pointers into both until the batch completes:
         # keep the Python objects alive until then (FIFO, as completions)
         self._inflight.append((pkts, out))
@@ -1161,11 +914,9 @@ class RxContext:
     def complete_host(self):
         """pptk_rx_batch_complete: wait for the oldest outstanding batch;
         returns its frame count."""
-        rc = self._L.pptk_rx_batch_complete(self._ctx)
-        if rc < 0:
-            raise OSError(-rc, f"pptk_rx_batch_complete failed ({rc})")
+        n = _check(self._L.pptk_rx_batch_complete(self._ctx), "pptk_rx_batch_complete", True)
         self._inflight.popleft()
-        return rc
+        return n
 
     def pending_host(self):
         return self._L.pptk_rx_batch_pending(self._ctx)
@@ -1174,10 +925,7 @@ class RxContext:
 def _flow_key(key):
     """One struct pptk_flow_key as a 40-byte uint8 array, from a
     records.FLOW_KEY_DTYPE entry or its bytes."""
-    k = np.frombuffer(key.tobytes() if hasattr(key, "tobytes") else bytes(key), np.uint8)
-    if k.size != 40:
-        raise ValueError("key must be one struct pptk_flow_key (40 bytes)")
-    return k
+    return _one_struct(key, "key", "pptk_flow_key", 40)
 
 
 def flow_key_hash(key16, key, lib_path=None):
@@ -1194,9 +942,7 @@ def flow_key_from_rec(rec, lib_path=None):
     """pptk_flow_key_from_rec: the records.FLOW_KEY_DTYPE entry of one record
     (a records.REC_DTYPE entry or its 64 bytes)."""
     from .records import FLOW_KEY_DTYPE
-    r = np.frombuffer(rec.tobytes() if hasattr(rec, "tobytes") else bytes(rec), np.uint8)
-    if r.size != 64:
-        raise ValueError("rec must be one struct pptk_rx_rec (64 bytes)")
+    r = _one_struct(rec, "rec", "pptk_rx_rec", 64)
     k = np.full(1, 0xEE, np.uint8).repeat(40)
     lib(lib_path).pptk_flow_key_from_rec(r.ctypes.data, k.ctypes.data)
     return k.view(FLOW_KEY_DTYPE)[0]
@@ -1211,14 +957,11 @@ class FlowTable:
 
     def __init__(self, slots, ctx=None, lib_path=None):
         self._L = L = ctx._L if ctx is not None else lib(lib_path)
-        if not hasattr(L, "pptk_flow_table_create"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_flow_table_create")
         self._t = ctypes.c_void_p()
         self._ctx = ctx   # (keeps the context alive as long as the table)
-        rc = L.pptk_flow_table_create(ctx._ctx if ctx is not None else None, slots,
-                                      ctypes.byref(self._t))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_table_create({slots}) failed ({rc})")
+        _check(L.pptk_flow_table_create(ctx._ctx if ctx is not None else None, slots,
+                                        ctypes.byref(self._t)),
+               f"pptk_flow_table_create({slots})")
 
     def close(self):
         if self._t:
@@ -1245,19 +988,13 @@ class FlowTable:
         return self._L.pptk_flow_table_delete(self._t, k.ctypes.data, flow_hash)
 
     def insert(self, key, flow_hash, value):
-        rc = self.insert_rc(key, flow_hash, value)
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_table_insert failed ({rc})")
+        _check(self.insert_rc(key, flow_hash, value), "pptk_flow_table_insert")
 
     def update(self, key, flow_hash, value):
-        rc = self.update_rc(key, flow_hash, value)
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_table_update failed ({rc})")
+        _check(self.update_rc(key, flow_hash, value), "pptk_flow_table_update")
 
     def delete(self, key, flow_hash):
-        rc = self.delete_rc(key, flow_hash)
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_table_delete failed ({rc})")
+        _check(self.delete_rc(key, flow_hash), "pptk_flow_table_delete")
 
     def find(self, key, flow_hash):
         """The key's value, or None if it is absent."""
@@ -1266,8 +1003,7 @@ class FlowTable:
         rc = self._L.pptk_flow_table_find(self._t, k.ctypes.data, flow_hash, ctypes.byref(v))
         if rc == -2:
             return None
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_table_find failed ({rc})")
+        _check(rc, "pptk_flow_table_find")
         return v.value
 
     def insert_recs(self, recs, values):
@@ -1279,10 +1015,9 @@ class FlowTable:
         if r.size != n * 64 or v.size != n:
             raise ValueError("insert_recs: n 64-byte records and n values")
         res = np.zeros(max(n, 1), np.int32)
-        rc = self._L.pptk_flow_table_insert_recs(self._t, r.ctypes.data, n, v.ctypes.data,
-                                                 res.ctypes.data)
-        if rc < 0:
-            raise OSError(-rc, f"pptk_flow_table_insert_recs failed ({rc})")
+        rc = _check(self._L.pptk_flow_table_insert_recs(self._t, r.ctypes.data, n, v.ctypes.data,
+                                                        res.ctypes.data),
+                    "pptk_flow_table_insert_recs", True)
         return rc, res[:n]
 
     def clear(self):
@@ -1297,16 +1032,10 @@ class FlowTable:
     def sync(self, stream=None):
         """pptk_flow_table_sync on `stream` (torch stream or None = current):
         the bytes it uploaded."""
-        if self._ctx is None:
-            s = None
-        else:
-            import torch
-            s = stream if stream is not None else torch.cuda.current_stream(self._ctx.device)
-            s = ctypes.c_void_p(s.cuda_stream)
+        s = None if self._ctx is None else _stream(stream, self._ctx.device)
         up = ctypes.c_uint64(0)
-        rc = self._L.pptk_flow_table_sync(self._t, s, ctypes.byref(up))
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_table_sync failed ({rc})")
+        _check(self._L.pptk_flow_table_sync(self._t, s, ctypes.byref(up)),
+               "pptk_flow_table_sync")
         return up.value
 
     def expire(self, stats, now, idle, cap=None):
@@ -1315,15 +1044,12 @@ class FlowTable:
         the downloaded copy -- with stats[v].last_seen + idle < now, and
         returns their values (uint32).  Call again while it returns cap
         values; sync() uploads the change."""
-        if not hasattr(self._L, "pptk_flow_table_expire"):
-            raise OSError(38, "this libpptkrx.so lacks pptk_flow_table_expire")
         st = _flow_stats(stats)
         cap = self.stats()["count"] if cap is None else cap
         out = np.zeros(max(cap, 1), np.uint32)
-        rc = self._L.pptk_flow_table_expire(self._t, st.ctypes.data, st.size, now, idle,
-                                            out.ctypes.data, cap)
-        if rc < 0:
-            raise OSError(-rc, f"pptk_flow_table_expire failed ({rc})")
+        rc = _check(self._L.pptk_flow_table_expire(self._t, st.ctypes.data, st.size, now, idle,
+                                                   out.ctypes.data, cap),
+                    "pptk_flow_table_expire", True)
         return out[:rc]
 
     def lookup_host(self, recs, subject=None):
@@ -1338,11 +1064,10 @@ class FlowTable:
             sub = np.ascontiguousarray(subject, dtype=np.uint8).reshape(-1)
             if sub.size != n:
                 raise ValueError("lookup_host: one subject byte per record")
-        rc = self._L.pptk_flow_lookup_host(self._t, r.ctypes.data, n,
-                                           None if sub is None else sub.ctypes.data,
-                                           idx.ctypes.data, st.ctypes.data)
-        if rc != 0:
-            raise OSError(-rc, f"pptk_flow_lookup_host failed ({rc})")
+        _check(self._L.pptk_flow_lookup_host(self._t, r.ctypes.data, n,
+                                             None if sub is None else sub.ctypes.data,
+                                             idx.ctypes.data, st.ctypes.data),
+               "pptk_flow_lookup_host")
         return idx[:n], st[:n]
 
 
@@ -1371,30 +1096,22 @@ def flow_account_host(idx, stats, now, lens=None, fixed_len=0, unmatched=None, l
     place: idx uint32, lens uint16 or None (then fixed_len), stats and
     unmatched (one entry, optional) aligned arrays of records.FLOW_STATS_DTYPE
     (flow_stats_array)."""
-    L = lib(lib_path)
-    if not hasattr(L, "pptk_flow_account_host"):
-        raise OSError(38, "this libpptkrx.so lacks pptk_flow_account_host")
     i = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
     ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint16).reshape(-1)
     if ln is not None and ln.size != i.size:
         raise ValueError("flow_account_host: one length per index")
     st = _flow_stats(stats)
     um = None if unmatched is None else _flow_stats(unmatched)
-    rc = L.pptk_flow_account_host(i.ctypes.data, None if ln is None else ln.ctypes.data, fixed_len,
-                                  i.size, st.ctypes.data, st.size,
-                                  None if um is None else um.ctypes.data, now)
-    if rc != 0:
-        raise OSError(-rc, f"pptk_flow_account_host failed ({rc})")
+    _check(lib(lib_path).pptk_flow_account_host(
+        i.ctypes.data, None if ln is None else ln.ctypes.data, fixed_len, i.size, st.ctypes.data,
+        st.size, None if um is None else um.ctypes.data, now), "pptk_flow_account_host")
 
 
 def flow_account_shape(lib_path=None):
     """pptk_flow_account_shape: (segment_frames, lds_slots) of the library's
     accounting kernel; lds_slots is 0 for a direct build."""
-    L = lib(lib_path)
-    if not hasattr(L, "pptk_flow_account_shape"):
-        raise OSError(38, "this libpptkrx.so lacks pptk_flow_account_shape")
     s, k = ctypes.c_uint32(), ctypes.c_uint32()
-    L.pptk_flow_account_shape(ctypes.byref(s), ctypes.byref(k))
+    lib(lib_path).pptk_flow_account_shape(ctypes.byref(s), ctypes.byref(k))
     return s.value, k.value
 
 
@@ -1412,9 +1129,6 @@ def flow_learn_host(recs, status, max_candidates, cap, lib_path=None):
     records.FLOW_LEARN_HDR_DTYPE entry, the arrays cut to hdr.written entries
     (records.REC_DTYPE, uint32, uint32)."""
     from .records import FLOW_LEARN_HDR_DTYPE, REC_DTYPE
-    L = lib(lib_path)
-    if not hasattr(L, "pptk_flow_learn_host"):
-        raise OSError(38, "this libpptkrx.so lacks pptk_flow_learn_host")
     r = np.ascontiguousarray(recs).view(np.uint8).reshape(-1)
     n = r.size // 64
     st = np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
@@ -1428,11 +1142,9 @@ def flow_learn_host(recs, status, max_candidates, cap, lib_path=None):
     first = np.zeros(max(cap, 1), np.uint32)
     packets = np.zeros(max(cap, 1), np.uint32)
     hdr = np.zeros(1, FLOW_LEARN_HDR_DTYPE)
-    rc = L.pptk_flow_learn_host(r.ctypes.data, st.ctypes.data, n, max_candidates,
-                                out.ctypes.data if cap else None, first.ctypes.data,
-                                packets.ctypes.data, cap, hdr.ctypes.data)
-    if rc != 0:
-        raise OSError(-rc, f"pptk_flow_learn_host failed ({rc})")
+    _check(lib(lib_path).pptk_flow_learn_host(
+        r.ctypes.data, st.ctypes.data, n, max_candidates, out.ctypes.data if cap else None,
+        first.ctypes.data, packets.ctypes.data, cap, hdr.ctypes.data), "pptk_flow_learn_host")
     w = int(hdr["written"][0])
     return hdr[0], out[:w * 64].view(REC_DTYPE), first[:w], packets[:w]
 
@@ -1440,20 +1152,14 @@ def flow_learn_host(recs, status, max_candidates, cap, lib_path=None):
 def flow_learn_scratch_bytes(n, max_candidates, lib_path=None):
     """pptk_flow_learn_scratch_bytes: the device scratch a learn call over n
     frames with this max_candidates needs (0 for n = 0)."""
-    L = lib(lib_path)
-    if not hasattr(L, "pptk_flow_learn_scratch_bytes"):
-        raise OSError(38, "this libpptkrx.so lacks pptk_flow_learn_scratch_bytes")
-    return L.pptk_flow_learn_scratch_bytes(n, max_candidates)
+    return lib(lib_path).pptk_flow_learn_scratch_bytes(n, max_candidates)
 
 
 def flow_learn_shape(lib_path=None):
     """pptk_flow_learn_shape: (block_frames, scan_width) of the library's
     learning kernels."""
-    L = lib(lib_path)
-    if not hasattr(L, "pptk_flow_learn_shape"):
-        raise OSError(38, "this libpptkrx.so lacks pptk_flow_learn_shape")
     b, w = ctypes.c_uint32(), ctypes.c_uint32()
-    L.pptk_flow_learn_shape(ctypes.byref(b), ctypes.byref(w))
+    lib(lib_path).pptk_flow_learn_shape(ctypes.byref(b), ctypes.byref(w))
     return b.value, w.value
 
 
@@ -1461,15 +1167,13 @@ def ip_fragment_host(frame, mtu, out_cap, out_stride=0, lib_path=None):
     """pptk_ip_fragment_host on one frame (bytes): (count, status, out,
     out_len) with out an (out_cap, out_stride) uint8 array pre-filled with
     0xEE whose rows [0, count) hold the fragments unless status has NOROOM."""
-    L = lib(lib_path)
     out_stride = out_stride or (18 + mtu + 15) & ~15
     out = np.full((max(out_cap, 1), out_stride), 0xEE, np.uint8)
     out_len = np.zeros(max(out_cap, 1), np.uint16)
     status = ctypes.c_uint8(0)
-    rc = L.pptk_ip_fragment_host(bytes(frame), len(frame), mtu, out.ctypes.data, out_stride,
-                                 out_cap, out_len.ctypes.data, ctypes.byref(status))
-    if rc < 0:
-        raise OSError(-rc, f"pptk_ip_fragment_host failed ({rc})")
+    rc = _check(lib(lib_path).pptk_ip_fragment_host(
+        bytes(frame), len(frame), mtu, out.ctypes.data, out_stride, out_cap, out_len.ctypes.data,
+        ctypes.byref(status)), "pptk_ip_fragment_host", True)
     return rc, status.value, out[:out_cap], out_len[:out_cap]
 
 
@@ -1478,31 +1182,24 @@ def tunnel_encap_host(frame, tun, seq=0, out_cap=None, lib_path=None):
     pptk_tunnel (a records.TUNNEL_DTYPE entry or its 32 bytes): (status, out,
     out_len) with out an out_cap-byte uint8 array (round_up(38 + len, 16)
     unless given) pre-filled with 0xEE."""
-    L = lib(lib_path)
-    if not hasattr(L, "pptk_tunnel_encap_host"):
-        raise OSError(38, "this libpptkrx.so lacks pptk_tunnel_encap_host")
-    t = np.frombuffer(tun.tobytes() if hasattr(tun, "tobytes") else bytes(tun), np.uint8)
-    if t.size != 32:
-        raise ValueError("tun must be one struct pptk_tunnel (32 bytes)")
+    t = _one_struct(tun, "tun", "pptk_tunnel", 32)
     frame = bytes(frame)
     if out_cap is None:
         out_cap = (38 + len(frame) + 15) & ~15
     out = np.full(max(out_cap, 1), 0xEE, np.uint8)
     out_len = ctypes.c_uint16(0xEEEE)
-    st = L.pptk_tunnel_encap_host(frame, len(frame), t.ctypes.data, seq, out.ctypes.data, out_cap,
-                                  ctypes.byref(out_len))
+    st = lib(lib_path).pptk_tunnel_encap_host(frame, len(frame), t.ctypes.data, seq,
+                                              out.ctypes.data, out_cap, ctypes.byref(out_len))
     return st, out[:out_cap], out_len.value
 
 
 def tunnel_decap_host(frame, lib_path=None):
     """pptk_tunnel_decap_host on one frame (bytes): (status, in_off, in_len),
     the inner frame being frame[in_off:in_off + in_len] when status has OK."""
-    L = lib(lib_path)
-    if not hasattr(L, "pptk_tunnel_decap_host"):
-        raise OSError(38, "this libpptkrx.so lacks pptk_tunnel_decap_host")
     frame = bytes(frame)
     in_off, in_len = ctypes.c_uint32(0xEEEEEEEE), ctypes.c_uint16(0xEEEE)
-    st = L.pptk_tunnel_decap_host(frame, len(frame), ctypes.byref(in_off), ctypes.byref(in_len))
+    st = lib(lib_path).pptk_tunnel_decap_host(frame, len(frame), ctypes.byref(in_off),
+                                              ctypes.byref(in_len))
     return st, in_off.value, in_len.value
 
 
@@ -1510,34 +1207,25 @@ def tcp_seq_translate_hdr(segment_bytes, xl, lib_path=None):
     """pptk_tcp_seq_translate_hdr on one TCP segment (bytes, the TCP header
     first) with the translation xl (one records.seqxlate_dtype entry, or its
     24 bytes): (status, the segment's bytes afterwards)."""
-    L = lib(lib_path)
-    if not hasattr(L, "pptk_tcp_seq_translate_hdr"):
-        raise OSError(38, "this libpptkrx.so lacks pptk_tcp_seq_translate_hdr")
-    x = np.frombuffer(xl.tobytes() if hasattr(xl, "tobytes") else bytes(xl), np.uint8)
-    if x.size != 24:
-        raise ValueError("xl must be one struct pptk_seqxlate (24 bytes)")
+    x = _one_struct(xl, "xl", "pptk_seqxlate", 24)
     # a buffer of exactly len(segment) bytes (at least one, to have an address)
     seg = np.frombuffer(bytes(segment_bytes), np.uint8).copy()
     buf = seg if seg.size else np.zeros(1, np.uint8)
-    st = L.pptk_tcp_seq_translate_hdr(buf.ctypes.data, seg.size, x.ctypes.data)
+    st = lib(lib_path).pptk_tcp_seq_translate_hdr(buf.ctypes.data, seg.size, x.ctypes.data)
     return st, seg.tobytes()
 
 
 def comm_uid(lib_path=None):
     """A new RCCL communicator id (128 bytes), made on one rank."""
     buf = ctypes.create_string_buffer(128)
-    rc = lib(lib_path).pptk_rx_comm_uid(buf)
-    if rc != 0:
-        raise OSError(-rc, f"pptk_rx_comm_uid failed ({rc})")
+    _check(lib(lib_path).pptk_rx_comm_uid(buf), "pptk_rx_comm_uid")
     return buf.raw
 
 
 def comm_create_all(ctxs):
     """One communicator over the contexts (one per GPU) of this process."""
     arr = (ctypes.c_void_p * len(ctxs))(*[c._ctx.value for c in ctxs])
-    rc = ctxs[0]._L.pptk_rx_comm_create_all(arr, len(ctxs))
-    if rc != 0:
-        raise OSError(-rc, f"pptk_rx_comm_create_all failed ({rc})")
+    _check(ctxs[0]._L.pptk_rx_comm_create_all(arr, len(ctxs)), "pptk_rx_comm_create_all")
 
 
 def shard_range(n, nranks, rank, lib_path=None):

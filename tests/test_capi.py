@@ -17,8 +17,11 @@ from conftest import ROOT, load_golden
 INCLUDE = os.path.join(ROOT, "include")
 
 
-def _declared_functions():
-    names = set()
+def _prototypes():
+    """{name: (return type, [parameter types])} of every function include/*.h
+    declares, the types as written minus the parameter names; an array
+    parameter reads as the pointer it is."""
+    protos = {}
     for h in glob.glob(os.path.join(INCLUDE, "*.h")):
         txt = open(h).read()
         txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
@@ -45,8 +48,34 @@ def _declared_functions():
             m = re.match(r"^((?:const )?(?:struct )?\w[\w \*]*?)\b(\w+) ?\(([^()]*)\)$", stmt)
             if not m or "static" in m.group(1) or "typedef" in m.group(1):
                 continue
-            names.add(m.group(2))
-    return names
+            params = []
+            if m.group(3).strip() != "void":
+                for p in m.group(3).split(","):
+                    t, _, arr = re.match(r"^(.*?)(\w+)(\[\w*\])?$", p.strip()).groups()
+                    params.append(t.strip() + (" *" if arr else ""))
+            protos[m.group(2)] = (m.group(1).strip(), params)
+    return protos
+
+
+def _declared_functions():
+    return set(_prototypes())
+
+
+C_SCALARS = {"uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
+             "uint16_t": ctypes.c_uint16, "uint8_t": ctypes.c_uint8,
+             "size_t": ctypes.c_size_t, "int": ctypes.c_int}
+
+
+def _ctype_agrees(ctype, decl):
+    """Whether `ctype` is how ctypes must pass or return the C type `decl`:
+    any pointer as c_void_p, c_char_p or a POINTER(...), a scalar as exactly
+    the type of its width and signedness, void (a return type) as None."""
+    if "*" in decl:
+        return ctype in (ctypes.c_void_p, ctypes.c_char_p) or (
+            isinstance(ctype, type) and issubclass(ctype, ctypes._Pointer))
+    if decl == "void":
+        return ctype is None
+    return ctype is C_SCALARS[decl.replace("const ", "")]
 
 
 @pytest.fixture(scope="module")
@@ -68,6 +97,28 @@ def test_library_exports_every_declared_function(lib):
 def test_exports_list_matches(lib):
     from pptk_amd import rx
     assert set(rx.EXPORTS) <= _declared_functions()
+
+
+def test_binding_signatures_match_the_headers(lib):
+    """Every function the Python binding exports is typed as its prototype
+    in include/*.h says: the parameter count, each parameter's and the return
+    value's kind.  (An untyped or mistyped uint64_t would reach C cut to an
+    int.)"""
+    from pptk_amd import rx
+    protos = _prototypes()
+    checked = 0
+    for name in rx.EXPORTS:
+        ret, params = protos[name]
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, name
+        assert len(fn.argtypes) == len(params), (name, params)
+        for k, (ctype, decl) in enumerate(zip(fn.argtypes, params)):
+            assert _ctype_agrees(ctype, decl), (name, k, decl, ctype)
+        assert _ctype_agrees(fn.restype, ret), (name, ret, fn.restype)
+        if ret == "const char *":
+            assert fn.restype is ctypes.c_char_p, name
+        checked += 1
+    assert checked == len(rx.EXPORTS) > 80
 
 
 def test_host_ip_cksum_feed_matches_oracle(lib, oracle_lib):
