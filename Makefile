@@ -61,7 +61,6 @@ hooks: $(HOOKS_LIB)
 all: $(HOOKS_LIB)
 
 # A/B builds of the product library with extra defines, e.g.
-#   make abvariant NAME=full DEFS=-DPPTK_RX_FULL_UNROLL
 #   make abvariant NAME=flow4 DEFS=-DPPTK_FLOW_TEAM=4   (rx_flow.hip: four lanes per record)
 #   make abvariant NAME=flowstat_direct DEFS=-DPPTK_FLOWSTAT_DIRECT=1   (rx_flowstat.hip: no LDS stage)
 abvariant:

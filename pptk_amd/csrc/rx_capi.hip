@@ -220,18 +220,12 @@ static int pick_variant(uint32_t span) {
   return RX_T64S2;
 }
 
-// The result-preserving memory-policy bits (pptk_rx.h).  The kernels also
-// know diagnostic bits that skip work (record stores, the per-frame phase,
-// half the record bytes, tx writes) for profiling; they are accepted only by
-// a -DPPTK_RX_DIAG build, so a product library can never produce wrong
-// records through pptk_rx_set_tuning or PPTK_RX_TUNE.
-#ifdef PPTK_RX_DIAG
-static constexpr uint32_t kTuneMask = 0xffffu;
-#else
+// The result-preserving memory-policy bits (pptk_rx.h): the only ones
+// pptk_rx_set_tuning and PPTK_RX_TUNE accept, so no tuning word can produce
+// wrong records.
 static constexpr uint32_t kTuneMask = PPTK_RX_TUNE_NT_LOADS | PPTK_RX_TUNE_NO_STAGING |
                                       PPTK_RX_TUNE_NT_STORES | PPTK_RX_TUNE_SC1_STORES |
                                       PPTK_RX_TUNE_BLOCKED | PPTK_RX_TUNE_PERMIT_PASSES;
-#endif
 
 // Memory policy (PPTK_RX_TUNE_*), from in-process A/B runs (DESIGN.md
 // "Measurement log"): non-temporal record stores always (C64 0.468 -> 0.463
@@ -267,8 +261,13 @@ static int forced_variant(const pptk_rx_ctx *c) {
   return force >= 0 && force < RX_NVARIANTS ? (int)force : -1;
 }
 
-// Blocks a launch may keep resident (the persistent grid).
-static uint64_t resident_blocks(const pptk_rx_ctx *c, int variant);
+// Blocks a launch may keep resident (the persistent grid): the variant's
+// blocks per CU on every CU but the ones pptk_rx_stream_split left to the
+// collective (the batches' stream cannot use them).
+static uint64_t resident_blocks(const pptk_rx_ctx *c, int variant) {
+  const uint64_t ncu = (uint64_t)std::max(1, c->ncu - std::min(c->coll_cus, c->ncu - 1));
+  return ncu * (uint64_t)c->bpc[variant];
+}
 
 // Grid of a launch: by default persistent (every block resident, its waves
 // striding over the tiles).  tpw > 0: enough blocks that each wave takes
@@ -286,27 +285,6 @@ static int grid_for(const pptk_rx_ctx *c, int variant, uint64_t n, uint32_t tpw 
   return (int)std::max<uint64_t>(1, std::min<uint64_t>(want_blocks, resident_blocks(c, variant)));
 }
 
-static uint64_t resident_blocks(const pptk_rx_ctx *c, int variant) {
-  static const long grid_mult = std::max(1l, EXP_KNOB("PPTK_RX_GRID_MULT", 1));
-  // the CUs pptk_rx_stream_split left to the collective (the batches'
-  // stream cannot use them); PPTK_RX_RESERVE_CUS: that many CUs' worth of
-  // resident blocks fewer without a mask (on its own it leaves no CU free:
-  // the dispatcher spreads the smaller grid over every CU)
-  static const int reserve_knob = (int)std::max(0l, EXP_KNOB("PPTK_RX_RESERVE_CUS", 0));
-  const int reserve = std::max(reserve_knob, c->coll_cus);
-  const uint64_t ncu = (uint64_t)std::max(1, c->ncu - std::min(reserve, c->ncu - 1));
-  // (PPTK_RX_BPC: resident blocks per CU for every variant, A/B only)
-  static const long bpc_knob = EXP_KNOB("PPTK_RX_BPC", 0);
-  const uint64_t bpc = bpc_knob > 0 ? (uint64_t)bpc_knob : (uint64_t)c->bpc[variant];
-  return ncu * bpc * (uint64_t)grid_mult;
-}
-
-// An oversubscribed launch's grid with its tail region (RxKArgs::tail_block):
-// the last PPTK_RX_TAIL_PCT % of the tiles in blocks of PPTK_RX_TAIL_TPW
-// tiles per wave, dispatched last, so that the launch does not end on a few
-// long blocks (A/B knobs; 0 % = one region).
-static int plan_grid(const pptk_rx_ctx *c, int variant, uint64_t n, uint32_t tpw, RxKArgs &a);
-
 // Tiles per wave of an oversubscribed grid (grid_for), 0 = persistent.  The
 // lane kernel, and the streaming shapes on offset-described batches (tiles
 // of uneven duration), run faster when the dispatcher hands out blocks of a
@@ -318,31 +296,9 @@ static int plan_grid(const pptk_rx_ctx *c, int variant, uint64_t n, uint32_t tpw
 // (4.1465 -> 4.3680), so fixed-stride streaming stays persistent, as does
 // the jumbo shape T64S2 (JMIX 3.9191 -> 4.0169 with 4 tiles, equal with 8).
 static uint32_t tiles_per_wave(int variant, bool gather) {
-  static const long lane = EXP_KNOB("PPTK_RX_LANE_TPW", 4);
-  static const long strm = EXP_KNOB("PPTK_RX_GATHER_TPW", 8);
-  static const long jumbo = EXP_KNOB("PPTK_RX_JUMBO_TPW", 0);   // T64S2 (A/B)
-  static const long fixed = EXP_KNOB("PPTK_RX_FIXED_TPW", 0);   // fixed stride (A/B)
-  if (variant == RX_L4) return (uint32_t)std::max(0l, lane);
-  if (!gather) return (uint32_t)std::max(0l, fixed);
-  return (uint32_t)std::max(0l, variant == RX_T64S2 ? jumbo : strm);
-}
-
-static int plan_grid(const pptk_rx_ctx *c, int variant, uint64_t n, uint32_t tpw, RxKArgs &a) {
-  a.tail_block = 0;
-  a.tail_tile = 0;
-  const int grid = grid_for(c, variant, n, tpw);
-  static const long pct = EXP_KNOB("PPTK_RX_TAIL_PCT", 0);
-  static const long ttpw = EXP_KNOB("PPTK_RX_TAIL_TPW", 1);
-  if (tpw == 0 || pct <= 0 || pct >= 100 || ttpw <= 0) return grid;
-  const uint64_t ntiles = (n + 63) / 64;
-  const uint64_t t2 = ntiles * (uint64_t)pct / 100, t1 = ntiles - t2;
-  const uint64_t w1 = (uint64_t)kWavesPerBlock * tpw, w2 = (uint64_t)kWavesPerBlock * (uint64_t)ttpw;
-  const uint64_t b1 = (t1 + w1 - 1) / w1, b2 = (t2 + w2 - 1) / w2;
-  // (a batch too small to fill the chip twice over keeps one region)
-  if (t2 == 0 || b1 < 2 * resident_blocks(c, variant) || b1 + b2 > 0x7fffffffull) return grid;
-  a.tail_block = (uint32_t)b1;
-  a.tail_tile = t1;
-  return (int)(b1 + b2);
+  if (variant == RX_L4) return 4;
+  if (!gather) return 0;
+  return variant == RX_T64S2 ? 0 : 8;
 }
 
 static uint64_t gcd64(uint64_t a, uint64_t b) {
@@ -413,8 +369,6 @@ static int auto_variant(const pptk_rx_dev_batch *b, bool *lane_ok_out) {
 // against 47-51 us tiles, CMIX 15-20 us against 20 us).  0 (off) for the
 // small-frame shapes, permuted batches (records scatter) and tx batches.
 static uint32_t phase_ticks_for(const pptk_rx_dev_batch *b, int variant, int grid) {
-  static const long force = EXP_KNOB("PPTK_RX_PHASE_TICKS", -1);
-  if (force >= 0) return (uint32_t)force;
   if (!rx_variant_phased(variant) || b->d_perm || (!b->d_recs && !b->d_recs32)) return 0;
   const uint64_t maxlen = b->d_len ? (b->max_len ? b->max_len : 1518u) : b->fixed_len;
   // (a stride far past any frame only lengthens the estimate; capped so the
@@ -427,37 +381,16 @@ static uint32_t phase_ticks_for(const pptk_rx_dev_batch *b, int variant, int gri
   return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ticks, 100), 1000000);
 }
 
-#ifdef PPTK_RX_WAVE_TIMES
-// probe build (tools/wave_times.py): every wave's (start, end) clock of the
-// last launch
-static uint64_t *g_wave_times = nullptr;
-static int g_wave_count = 0;
-extern "C" int pptk_rx_wave_times(uint64_t *host, int max_waves) {
-  if (!g_wave_times) return -EINVAL;
-  const int n = std::min(max_waves, g_wave_count);
-  if (hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpy(host, g_wave_times, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess)
-    return -EIO;
-  return n;
-}
-#endif
-
 static int launch_batch(pptk_rx_ctx *c, const pptk_rx_dev_batch *b, int variant, void *stream) {
   RxKArgs a = batch_args(c, b);
   a.tune = pick_tune(c, variant, b->d_off || b->d_len || b->d_perm,
                      variant == RX_L4 && lane_coalesced(b->stride, b->fixed_len));
   c->last_variant = variant;
   const bool gather = b->d_off || b->d_len || b->d_perm;
-  const int grid = plan_grid(c, variant, b->n, tiles_per_wave(variant, gather), a);
+  const int grid = grid_for(c, variant, b->n, tiles_per_wave(variant, gather));
   // (the period follows the waves resident at once, not the whole grid)
   a.phase_ticks = phase_ticks_for(
       b, variant, (int)std::min<uint64_t>((uint64_t)grid, resident_blocks(c, variant)));
-#ifdef PPTK_RX_WAVE_TIMES
-  if (!g_wave_times && hipMalloc(&g_wave_times, (size_t)65536 * 16) != hipSuccess) return -ENOMEM;
-  if (grid * kWavesPerBlock > 65536) return -EINVAL;
-  a.wave_times = g_wave_times;
-  g_wave_count = grid * kWavesPerBlock;
-#endif
   return hip_err(launch_rx(variant, a, grid, (hipStream_t)stream));
 }
 
@@ -628,13 +561,6 @@ int pptk_rx_place_records(struct pptk_rx_ctx *c, const struct pptk_rx_dev_batch 
 // frame's checksum fields in a side array (8 B per frame) and a second
 // kernel writes them, so that the 2-byte field writes do not land beside
 // the 25 GB read stream (DESIGN.md "Secondary kernels").
-// PPTK_TX_TWO_PASS=0: the fields are stored in place by the streaming pass
-// (A/B).
-static bool tx_two_pass() {
-  static const long v = EXP_KNOB("PPTK_TX_TWO_PASS", 1);
-  return v != 0;
-}
-
 int pptk_tx_cksum_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_t *d_off,
                          const uint16_t *d_len, uint64_t stride, uint32_t fixed_len,
                          uint64_t n, uint32_t max_len, void *stream) {
@@ -661,7 +587,7 @@ int pptk_tx_cksum_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_
   }
   const uint32_t maxlen = d_len ? (max_len ? max_len : 65535u) : fixed_len;
   int variant = pick_variant(maxlen + mmax);
-  const bool two_pass = !d_off && tx_two_pass();
+  const bool two_pass = !d_off;
   if (two_pass) {
     // the streaming pass of a two-pass batch moves what the receive
     // transform moves minus most of the writes: pptk_rx_autotune's choice
@@ -777,37 +703,9 @@ int pptk_tcp_seq_translate_device(struct pptk_rx_ctx *c, uint8_t *d_frames, cons
                 });
 }
 
-// The length groups of the mixed path: kGroupMaxLen, or (A/B experiment)
-// PPTK_RX_BIN_BOUNDS="b0,b1", non-decreasing upper bounds of groups 0 and 1
-// (equal neighbours leave a group empty; it is not launched).
-static const BinBounds &bin_bounds() {
-  static const BinBounds bb = [] {
-    BinBounds r;
-    for (int k = 0; k < kGroups - 1; ++k) r.b[k] = kGroupMaxLen[k];
-#ifdef PPTK_RX_EXPERIMENTS
-    const char *e = getenv("PPTK_RX_BIN_BOUNDS");
-#else
-    const char *e = nullptr;
-#endif
-    if (!e) return r;
-    BinBounds t = r;
-    for (int k = 0; k < kGroups - 1; ++k) {
-      char *end = nullptr;
-      const unsigned long v = strtoul(e, &end, 10);
-      if (end == e || v > 65535 || (k && v < t.b[k - 1])) return r;
-      t.b[k] = (uint32_t)v;
-      e = *end == ',' ? end + 1 : end;
-    }
-    return t;
-  }();
-  return bb;
-}
-
-static bool default_bounds(const BinBounds &bb) {
-  for (int k = 0; k < kGroups - 1; ++k)
-    if (bb.b[k] != kGroupMaxLen[k]) return false;
-  return true;
-}
+// The length groups of the mixed path, as launch_bin takes them.
+static_assert(kGroups == 3, "kBinBounds lists the bounds of groups 0 and 1");
+static constexpr BinBounds kBinBounds = {{kGroupMaxLen[0], kGroupMaxLen[1]}};
 
 int pptk_rx_batch_device_mixed(struct pptk_rx_ctx *c, const struct pptk_rx_dev_batch *b,
                                uint32_t *d_perm, void *d_scratch, void *stream) {
@@ -817,9 +715,7 @@ int pptk_rx_batch_device_mixed(struct pptk_rx_ctx *c, const struct pptk_rx_dev_b
   DeviceScope dg(c->device);
   if (!dg.ok) return -EIO;
   const hipStream_t s = (hipStream_t)stream;
-  const BinBounds &bb = bin_bounds();
-  const bool dflt = default_bounds(bb);
-  if (b->max_len && b->max_len <= bb.b[kGroups - 2]) {
+  if (b->max_len && b->max_len <= kGroupMaxLen[kGroups - 2]) {
     // Every frame fits the 1536-byte shape (by the hint; a wrong hint costs
     // speed, never results): no length group is worth a launch of its own
     // (DESIGN.md "Binned order"), so batch order, as pptk_rx_batch_device.
@@ -833,7 +729,7 @@ int pptk_rx_batch_device_mixed(struct pptk_rx_ctx *c, const struct pptk_rx_dev_b
   // the group launches stream them instead of gathering them through perm
   BinDesc bd{b->d_off, b->stride, bin_desc_off(d_scratch, kBinGrid),
              bin_desc_len(d_scratch, kBinGrid, b->n)};
-  hipError_t e = launch_bin(b->d_len, b->n, perm, d_scratch, s, kBinGrid, bd, bb, true);
+  hipError_t e = launch_bin(b->d_len, b->n, perm, d_scratch, s, kBinGrid, bd, kBinBounds, true);
   if (e != hipSuccess) return -EIO;
   RxKArgs a = batch_args(c, b);
   a.perm = perm;
@@ -849,11 +745,8 @@ int pptk_rx_batch_device_mixed(struct pptk_rx_ctx *c, const struct pptk_rx_dev_b
   for (int g = 0; g < kGroups; ++g) {
     // the group holding max_len also takes every group above it (all empty
     // when the hint is right; a wrong hint costs speed, never results)
-    const bool last = g == kGroups - 1 || bb.b[g] >= maxlen;
-    if (!last && g > 0 && bb.b[g] == bb.b[g - 1]) continue;   // empty by its bounds
-    int variant = fv >= 0 && fv != RX_L4 ? fv
-                  : dflt || g == kGroups - 1 ? kGroupVariant[g]
-                                             : pick_variant(bb.b[g] + 15);
+    const bool last = kGroupMaxLen[g] >= maxlen;
+    int variant = fv >= 0 && fv != RX_L4 ? fv : kGroupVariant[g];
     // (a launch may run the whole batch when it is not binned:
     // pptk_rx_autotune's choice for its shape applies, as in batch order)
     if (fv < 0 && c->tuned[1][variant] >= 0 && c->tuned[1][variant] != RX_L4)
@@ -1035,7 +928,7 @@ int pptk_rx_bin_device(struct pptk_rx_ctx *c, const uint16_t *d_len, uint64_t n,
   DeviceScope dg(c->device);
   if (!dg.ok) return -EIO;
   return hip_err(launch_bin(d_len, n, d_perm, d_scratch, (hipStream_t)stream, kBinGrid,
-                            BinDesc{nullptr, 0, nullptr, nullptr}, bin_bounds(), false));
+                            BinDesc{nullptr, 0, nullptr, nullptr}, kBinBounds, false));
 }
 
 }  // extern "C"

@@ -58,23 +58,6 @@
 
 using namespace pptk;
 
-// Experiment builds: PPTK_RX_COMM_TRACE=1 traces the communicator calls.
-#ifdef PPTK_RX_EXPERIMENTS
-#include <stdio.h>
-#define COMM_TRACE(...)                                              \
-  do {                                                               \
-    static const bool on_ = getenv("PPTK_RX_COMM_TRACE") != nullptr; \
-    if (on_) {                                                       \
-      fprintf(stderr, "[pptk comm] " __VA_ARGS__);                   \
-      fputc('\n', stderr);                                           \
-    }                                                                \
-  } while (0)
-#else
-#define COMM_TRACE(...) \
-  do {                  \
-  } while (0)
-#endif
-
 namespace {
 
 // The RCCL entry points used here, resolved once from librccl.so.1.
@@ -236,9 +219,6 @@ ncclConfig_t comm_config(int coll_cus) {
   ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
   cfg.blocking = 0;
   if (coll_cus > 0) cfg.maxCTAs = coll_cus;
-#ifdef PPTK_RX_EXPERIMENTS
-  if (getenv("PPTK_RX_COMM_BLOCKING")) cfg.blocking = 1;
-#endif
   return cfg;
 }
 
@@ -318,7 +298,6 @@ void init_run(const Rccl *R, std::shared_ptr<InitJob> job, ncclUniqueId id,
     const ncclResult_t re = R->GroupEnd();
     if (going(r)) r = re;
   }
-  COMM_TRACE("init job: init calls returned %d", (int)r);
   // a non-blocking init goes on in RCCL: poll until it is done, or until
   // the caller has given up
   Backoff b;
@@ -406,7 +385,6 @@ void init_run(const Rccl *R, std::shared_ptr<InitJob> job, ncclUniqueId id,
       if (idle && buf[i]) (void)hipFree(buf[i]);
       if (idle && st[i]) (void)hipStreamDestroy(st[i]);
     }
-    COMM_TRACE("init job: warm-up gather %d", (int)r);
   }
   bool abandoned;
   {
@@ -419,7 +397,6 @@ void init_run(const Rccl *R, std::shared_ptr<InitJob> job, ncclUniqueId id,
     }
   }
   if (abandoned) {   // the caller returned -ETIMEDOUT / -ECANCELED: nobody owns these
-    COMM_TRACE("init job: abandoned, aborting");
     for (size_t i = 0; i < k; ++i)
       if (comms[i] && hipSetDevice(devs[i]) == hipSuccess) (void)R->CommAbort(comms[i]);
     g_abandoned.fetch_sub(1);
@@ -450,7 +427,6 @@ int bounded_init(const Rccl *R, const std::shared_ptr<InitJob> &job, const ncclU
   if (!job->done) {
     job->abandoned = true;   // the helper aborts what it builds and counts itself out
     g_abandoned.fetch_add(1);
-    COMM_TRACE("create: %s, init abandoned", done ? "cancelled" : "deadline passed");
     return done ? -ECANCELED : -ETIMEDOUT;
   }
   const ncclResult_t r = job->r;
@@ -608,11 +584,9 @@ int pptk_rx_comm_create(struct pptk_rx_ctx *c, int nranks, int rank,
   ms[0]->rank = rank;
   ncclUniqueId id;
   memcpy(&id, uid, sizeof(id));
-  COMM_TRACE("create: init rank %d of %d", rank, nranks);
   std::vector<ncclComm_t> comms;
   rc = bounded_init(R, job, id, {ctx_device(c)}, {rank}, {ctx_coll_cap(c)}, nranks,
                     ctx_comm_timeout_ms(c), comms);
-  COMM_TRACE("create: %d", rc);
   return end_create(R, &c, 1, ms, comms, rc);
 }
 

@@ -141,17 +141,16 @@ static bool fit_span(RxSlot &sl, size_t bytes) {
 // moves ~48 GB/s of frames by DMA, the kernel's own reads of host memory
 // ~37-38, so the break-even is near 80 % (1500-byte frames in 2 KB netmap
 // slots, 73 %, measured 37 GB/s by DMA against 38 in place).
-// A/B: PPTK_RX_SPLIT=0 restores the descriptor and record copies (~0.18 ms of
-// copy-engine time per 65 536-frame chunk beside its 2.2 ms frame copy),
-// PPTK_RX_UNIFORM=0 turns fixed-stride chunks off, PPTK_RX_NT_GATHER=0
-// gathers with plain memcpy.
+// split, uniform and nt_gather are always on: without the split the
+// descriptor and record copies cost ~0.18 ms of copy-engine time per
+// 65 536-frame chunk beside its 2.2 ms frame copy.
 static const HostKnobs &host_knobs() {
   static const HostKnobs k = {
       (size_t)std::max(0l, env_long("PPTK_RX_DIRECT_MAX_BYTES", 2l << 20)),
       env_long("PPTK_RX_RING_DMA_PCT", 80) / 100.0,
-      EXP_KNOB("PPTK_RX_SPLIT", 1) != 0,
-      EXP_KNOB("PPTK_RX_UNIFORM", 1) != 0,
-      EXP_KNOB("PPTK_RX_NT_GATHER", 1) != 0,
+      true,   // split
+      true,   // uniform
+      true,   // nt_gather
   };
   return k;
 }
@@ -176,9 +175,6 @@ static WorkerPool *pool_of(HostPipe *hp, const pptk_rx_opts &o) {
 // cost).
 static void copy_out(WorkerPool *pool, void *dst, const void *src, size_t n) {
   constexpr size_t kPiece = 1u << 20;
-#ifdef PPTK_RX_SERIAL_COPYOUT
-  pool = nullptr;
-#endif
   if (!pool || n < 2 * kPiece) {
     memcpy(dst, src, n);
     return;

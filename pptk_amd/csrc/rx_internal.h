@@ -57,25 +57,6 @@ inline long env_long(const char *name, long dflt) {
   return e ? atol(e) : dflt;
 }
 
-// Diagnostic tune bits (RxKArgs::tune 3, 4, 7, 9: skip record stores, the
-// per-frame phase, half the record bytes, the tx writes -- output invalid,
-// for profiling) and the A/B environment knobs of the host code exist only
-// in experiment builds (`make abvariant NAME=exp DEFS=-DPPTK_RX_EXPERIMENTS`):
-// in the product library the branches are compiled out and the knobs are
-// constants (INTEGRATION.md section 6 lists the knobs a product build reads).
-#if defined(PPTK_RX_EXPERIMENTS) || defined(PPTK_RX_DIAG)
-constexpr bool kDiag = true;
-#else
-constexpr bool kDiag = false;
-#endif
-// An A/B knob: read from the environment in experiment builds only; a product
-// build uses the default.
-#ifdef PPTK_RX_EXPERIMENTS
-#define EXP_KNOB(name, dflt) env_long(name, dflt)
-#else
-#define EXP_KNOB(name, dflt) ((long)(dflt))
-#endif
-
 // Kernel arguments (by value; a handful of SGPRs).
 struct RxKArgs {
   const uint8_t *frames;
@@ -126,14 +107,12 @@ struct RxKArgs {
   // global write phases of the streaming shapes (rx_kernel.hip): the period
   // in s_memrealtime ticks (10 ns); 0 = each tile's records at its end
   uint32_t phase_ticks;
-  // oversubscribed grids (rx_capi.hip grid_for): blocks from tail_block on
-  // (0: none) take the tiles from tail_tile on, in fewer tiles per wave, so
-  // that the launch's last blocks are short
+  // a tail region of short blocks for oversubscribed grids (blocks from
+  // tail_block on took the tiles from tail_tile on) measured no gain
+  //  and no launch sets it any more:
+  // always 0; kept so the device code is unchanged
   uint32_t tail_block;
   uint64_t tail_tile;
-#ifdef PPTK_RX_WAVE_TIMES
-  uint64_t *wave_times;   // probe build: per wave (start, end) of the last launch
-#endif
 };
 
 // Kernel variants: T lanes per frame in the streaming checksum phase, S
@@ -150,20 +129,13 @@ enum RxVariant {
 };
 
 // Wavefronts per block of the receive kernels (every wave works on its own
-// tiles; no block-wide barrier).  PPTK_RX_WPB builds another size (A/B).
-#ifndef PPTK_RX_WPB
-#define PPTK_RX_WPB 4
-#endif
-constexpr int kWavesPerBlock = PPTK_RX_WPB;
+// tiles; no block-wide barrier).
+constexpr int kWavesPerBlock = 4;
 
 // The lane kernel reads a batch packed at a 64-byte stride whose frames all
-// span four chunks as contiguous 4 KB tiles (rx_kernel.hip lane_load);
-// PPTK_RX_LANE_COAL=0 builds the per-frame loads only (A/B).
-#ifndef PPTK_RX_LANE_COAL
-#define PPTK_RX_LANE_COAL 1
-#endif
+// span four chunks as contiguous 4 KB tiles (rx_kernel.hip lane_load).
 __host__ __device__ inline bool lane_coalesced(uint64_t stride, uint32_t fixed_len) {
-  return PPTK_RX_LANE_COAL && stride == 64 && ((fixed_len + 15u) >> 4) == 4;
+  return stride == 64 && ((fixed_len + 15u) >> 4) == 4;
 }
 
 // Length groups of pptk_rx_batch_device_mixed: group g holds the frames with

@@ -45,25 +45,18 @@ namespace {
 constexpr int WAVE = 64;
 constexpr int WPB = kWavesPerBlock;   // waves per block (4: 256 threads)
 constexpr int IMG_CHUNKS = 8;     // 16-byte chunks parked in LDS per frame
-#ifndef PPTK_RX_IMG_STRIDE
-#define PPTK_RX_IMG_STRIDE 144
-#endif
 // LDS bytes per frame slot.  144 = 9 x 16: no b128 bank conflicts when a
 // team parks its chunks; an odd dword pitch (148) instead spreads the
 // per-frame phase's byte reads (every lane reading the same offset of its
 // own frame) over all banks, at the price of parking chunks as dwords:
 // measured equal (CMIX 2.717 vs 2.721 ms, C1500 4.161 vs 4.160 ms,
 // in-process A/B) -- the per-frame phase is hidden behind the streaming --
-// so 144 stays.
-constexpr int IMG_STRIDE = PPTK_RX_IMG_STRIDE;
+// so 144 stayed.
+constexpr int IMG_STRIDE = 144;
 // Offset-described batches: where the team parks a frame's last chunk in the
-// frame's slot (rx_kernel); PPTK_RX_TAIL_LDS=0 (A/B) corrects in the round.
-#ifndef PPTK_RX_TAIL_LDS
-#define PPTK_RX_TAIL_LDS 1
-#endif
-constexpr bool TAIL_LDS = PPTK_RX_TAIL_LDS;
+// frame's slot (rx_kernel).
 constexpr int TAIL_OFF = 128;
-static_assert(!TAIL_LDS || (IMG_STRIDE >= TAIL_OFF + 16 && IMG_STRIDE % 16 == 0),
+static_assert(IMG_STRIDE >= TAIL_OFF + 16 && IMG_STRIDE % 16 == 0,
               "the parked tail chunk lives past the 128-byte image");
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
@@ -541,7 +534,7 @@ __device__ __forceinline__ void lane_generic(const RxKArgs &a, const FrameView &
     }
     if (a.txside)
       o.tx = tx_entry(txp, txv);
-    else if (a.frames_w && !(kDiag && (a.tune & 512u)))   // bit 9: diagnostics, no tx writes
+    else if (a.frames_w)
       tx_store(a, base, txp, txv);
     uint32_t bucket = 0;
     if (a.recs || a.recs32 || a.hash) {   // tx batches need no hashes
@@ -658,14 +651,6 @@ __device__ __forceinline__ bool lane_fast(const RxKArgs &a, const uint32_t d[16]
   return true;
 }
 
-// How the kernel writes the dense flow-hash array (A/B builds: 0 plain
-// per-lane stores, 1 non-temporal per-lane stores, 2 staged beside the
-// record and stored by flush_records as one run per tile).
-#ifndef PPTK_RX_HASH_MODE
-#define PPTK_RX_HASH_MODE 2
-#endif
-
-
 // Record of frame `idx`: the optional dense flow-hash word, then the record
 // (64 bytes, or the 32-byte compact projection) either parked in the lane's
 // LDS slot `st` for flush_records (batch order) or stored directly
@@ -679,9 +664,9 @@ __device__ __forceinline__ void emit_record(const RxKArgs &a, const LaneRec &o, 
   // order) parked in the record slot's spare 16 bytes and stored by the
   // flush as one 512-byte run per tile next to the tile's records.
   if (a.hash) {
-    if (PPTK_RX_HASH_MODE == 2 && stage && !a.perm)
+    if (stage && !a.perm)
       *(LDS_AS uint64_t *)(st + 4) = o.fh;
-    else if (PPTK_RX_HASH_MODE >= 1 && (a.tune & 32u))
+    else if (a.tune & 32u)
       __builtin_nontemporal_store(o.fh, (GLB_AS uint64_t *)a.hash + idx);
     else
       a.hash[idx] = o.fh;
@@ -739,8 +724,7 @@ __device__ __forceinline__ void flush_records(const RxKArgs &a, const LDS_AS uin
   GLB_AS u32x4 *dst = (GLB_AS u32x4 *)(rbase + tile * (uint64_t)WAVE * (c32 ? 32u : 64u));
   const uint64_t nrec = min((uint64_t)WAVE, a.n - tile * WAVE);
   const int lg = c32 ? 1 : 2;                 // log2 16-byte pieces per record
-  int kmax = c32 ? 2 : 4;
-  if (kDiag && (a.tune & 128u)) kmax >>= 1;   // bit 7: diagnostics, half the bytes
+  const int kmax = c32 ? 2 : 4;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int e = k * WAVE + lane;   // 16-byte piece e of the tile's records
@@ -775,7 +759,7 @@ __device__ __forceinline__ void flush_records(const RxKArgs &a, const LDS_AS uin
   // lanes 0..31 store two records' hashes each, one 512-byte run
   // (the same condition as emit_record's: !a.perm -- a permuted batch
   // stored its hashes per lane)
-  if (PPTK_RX_HASH_MODE == 2 && a.hash && !scatter && !a.perm && lane < WAVE / 2) {
+  if (a.hash && !scatter && !a.perm && lane < WAVE / 2) {
     const uint32_t r0 = 2u * (uint32_t)lane;
     if ((uint64_t)r0 < nrec) {
       const uint64_t h0 = *(const LDS_AS uint64_t *)(st + r0 * 5 + 4);
@@ -831,9 +815,10 @@ __device__ __forceinline__ void flush_stash(const RxKArgs &a, const LDS_AS u32x4
 }
 
 // The tiles of wave `wv` of this block: first, first + step, ... below end.
-// Strided over the grid by default; with a tail region (RxKArgs::tail_block)
-// the blocks before it stride over the tiles before tail_tile and the ones
-// from it on over the rest; with tune bit 8 (experiment) a contiguous run.
+// Strided over the grid by default; with a tail region (RxKArgs::tail_block,
+// which no launch sets any more) the blocks before it stride over the tiles
+// before tail_tile and the ones from it on over the rest; with tune bit 8
+// (PPTK_RX_TUNE_BLOCKED) a contiguous run.
 struct TileRange {
   uint64_t first, step, end;
 };
@@ -861,11 +846,8 @@ __device__ __forceinline__ uint64_t pf_tile(const TileRange &r, uint64_t ntiles,
 // need 2 waves/SIMD; the small-frame variants 4.
 template <int T, int S>
 constexpr int min_waves_per_simd() { return S * T >= 32 ? 2 : 4; }
-#ifndef PPTK_RX_D1_WAVES
-#define PPTK_RX_D1_WAVES 3
-#endif
 template <int T, int S, int D>
-constexpr int min_waves() { return D == 1 && S * T >= 32 ? PPTK_RX_D1_WAVES : min_waves_per_simd<T, S>(); }
+constexpr int min_waves() { return D == 1 && S * T >= 32 ? 3 : min_waves_per_simd<T, S>(); }
 
 // D = rounds in flight; (D + 1) must divide T so that the prefetch ring is
 // back in its starting registers at the tile boundary (no moves of in-flight
@@ -936,10 +918,6 @@ __global__ __launch_bounds__(WAVE * WPB, (min_waves<T, S, D>())) void rx_kernel(
   const uint64_t step = tr.step, tend = tr.end;
 
   uint64_t tile = tr.first;
-#ifdef PPTK_RX_WAVE_TIMES
-  const uint64_t wid = (uint64_t)blockIdx.x * WPB + wv;
-  const uint64_t wt_start = __builtin_amdgcn_s_memrealtime();
-#endif
   Desc dc = load_desc<GATHER>(a, pf_tile(tr, ntiles, tile), lane);
   Desc dn = load_desc<GATHER>(a, pf_tile(tr, ntiles, tile + step), lane);
   uint32_t idx2 = desc_idx<GATHER>(a, pf_tile(tr, ntiles, tile + 2 * step), lane);
@@ -984,17 +962,7 @@ __global__ __launch_bounds__(WAVE * WPB, (min_waves<T, S, D>())) void rx_kernel(
         for (int s = 0; s < S; ++s) {
           if (s * T < IMGC + (int)(ALM >> 4)) {
             const int ci = s * T + j - c_img;      // image = 16-byte chunks from floor16(frame)
-            if (ci >= 0 && ci < IMGC) {
-              if constexpr (IMG_STRIDE % 16 == 0) {
-                *(LDS_AS u32x4 *)(img + 16 * ci) = cb.v[s];
-              } else {
-                LDS_AS uint32_t *w = (LDS_AS uint32_t *)(img + 16 * ci);
-                w[0] = cb.v[s].x;
-                w[1] = cb.v[s].y;
-                w[2] = cb.v[s].z;
-                w[3] = cb.v[s].w;
-              }
-            }
+            if (ci >= 0 && ci < IMGC) *(LDS_AS u32x4 *)(img + 16 * ci) = cb.v[s];
           }
         }
         uint32_t acc = 0;
@@ -1016,15 +984,8 @@ __global__ __launch_bounds__(WAVE * WPB, (min_waves<T, S, D>())) void rx_kernel(
           // the last chunk, load_round): it parks it in the frame's image
           // slot (bytes 128..143), where the owning lane takes those bytes
           // off in the lane phase -- no second read of the chunk from
-          // memory, one LDS store per round.  (TAIL_LDS 0, A/B: the same
-          // correction here, every lane computing it, every round; a lane's
-          // partial may wrap below zero, the team's u32 total cannot.)
-          if constexpr (TAIL_LDS) {
-            if (j == T - 1) *(LDS_AS u32x4 *)(img + TAIL_OFF) = cb.v[S - 1];
-          } else {
-            const uint32_t corr = tail_past_end(cb.v[S - 1], m, (int)cb.pl, ts);
-            acc -= (j == T - 1 && nch <= S * T) ? corr : 0u;
-          }
+          // memory, one LDS store per round.
+          if (j == T - 1) *(LDS_AS u32x4 *)(img + TAIL_OFF) = cb.v[S - 1];
         }
         acc = team_sum<T>(acc);
         if (j == r)
@@ -1040,11 +1001,7 @@ __global__ __launch_bounds__(WAVE * WPB, (min_waves<T, S, D>())) void rx_kernel(
         }
       }
     };
-#ifdef PPTK_RX_FULL_UNROLL
-#pragma unroll(T <= 16 ? T : 1)
-#else
 #pragma unroll 1
-#endif
     for (int r0 = 0; r0 < T - (D + 1); r0 += D + 1) {
       group(r0);
       if (PHASED && st_tile != ~0ull && __builtin_amdgcn_s_memrealtime() >= st_deadline) {
@@ -1062,15 +1019,14 @@ __global__ __launch_bounds__(WAVE * WPB, (min_waves<T, S, D>())) void rx_kernel(
     // ---- lane phase: frame `lane` -> record (parsed once per frame)
     const bool stage = !(a.tune & 2u);
     const bool scatter = GATHER && a.perm;
-    // tune bit 4 (diagnostics only, output invalid): skip the lane phase
-    if (dc.idx != 0xffffffffu && !(kDiag && (a.tune & 16u))) {
+    if (dc.idx != 0xffffffffu) {
       const int m = (int)(dc.base & 15);
       const int ma = (int)(dc.base & ALM);
       const int nch = (ma + (int)dc.len + 15) >> 4;
       // the frame's last chunk as its team parked it (frames that fit the
       // round; longer ones were summed masked)
       u32x4 tailc = (u32x4){0u, 0u, 0u, 0u};
-      if constexpr (GATHER && TAIL_LDS) {
+      if constexpr (GATHER) {
         const u32x4 t = *(const LDS_AS u32x4 *)(wimg + lane * IMG_STRIDE + TAIL_OFF);
         const bool fits = nch <= S * T;
         tailc = (u32x4){fits ? t.x : 0u, fits ? t.y : 0u, fits ? t.z : 0u, fits ? t.w : 0u};
@@ -1093,7 +1049,7 @@ __global__ __launch_bounds__(WAVE * WPB, (min_waves<T, S, D>())) void rx_kernel(
       // program order) for the coalesced store below
       emit_record(a, o, dc.idx, (LDS_AS u32x4 *)wimg + lane * 5, stage);
     }
-    if (stage && !(kDiag && (a.tune & 8u)) && (a.recs || a.recs32)) {  // tune bit 3: diagnostics, no stores
+    if (stage && (a.recs || a.recs32)) {
       if (PHASED && phased && !scatter) {
         if (st_tile != ~0ull) flush_stash(a, stash, st_tile, lane);   // the stash is needed
         flush_records(a, wimg, tile, lane, dc.idx, scatter, stash);
@@ -1109,13 +1065,6 @@ __global__ __launch_bounds__(WAVE * WPB, (min_waves<T, S, D>())) void rx_kernel(
     idx2 = idx3;
   }
   if (PHASED && st_tile != ~0ull) flush_stash(a, stash, st_tile, lane);
-#ifdef PPTK_RX_WAVE_TIMES
-  // probe build (tools/wave_times.py): when each wave started and finished
-  if (a.wave_times && lane == 0) {
-    a.wave_times[2 * wid] = wt_start;
-    a.wave_times[2 * wid + 1] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 // ---- Mixed-shape kernel (RX_M6): lanes binned by length inside each tile.
@@ -1148,13 +1097,8 @@ constexpr int M_S = 6;        // chunk loads per lane per round
 // (141 VGPRs) beat three at 2 waves/SIMD (195) and two at 2 or 3 (168):
 // IMIX 1.537 / 1.475 / 1.451 ms for D = 3 / 2 / 1, CMIX 2.891 / 2.864 /
 // 2.865 ms (in-process A/B, profiles/r03/m6/m6d_ab_*.json).
-#ifndef PPTK_RX_M_D
-#define PPTK_RX_M_D 1
-#endif
-#ifndef PPTK_RX_M_WAVES
-#define PPTK_RX_M_WAVES 3
-#endif
-constexpr int M_D = PPTK_RX_M_D;   // rounds in flight
+constexpr int M_D = 1;        // rounds in flight
+constexpr int M_WAVES = 3;    // waves per SIMD the registers must allow
 constexpr int M_SUM = 128;    // byte offset of a frame's team sum in its image slot
 static_assert(IMG_STRIDE >= M_SUM + 4, "the team sum lives past the 128-byte image");
 
@@ -1270,7 +1214,7 @@ __device__ __forceinline__ MBuf m_load_round(const RxKArgs &a, const Desc &d, co
 }
 
 template <bool NT, bool GATHER>
-__global__ __launch_bounds__(WAVE * WPB, PPTK_RX_M_WAVES) void rx_kernel_mixed(RxKArgs a) {
+__global__ __launch_bounds__(WAVE * WPB, M_WAVES) void rx_kernel_mixed(RxKArgs a) {
   if constexpr (GATHER) {
     if (!group_range(a)) return;
   }
@@ -1378,7 +1322,7 @@ __global__ __launch_bounds__(WAVE * WPB, PPTK_RX_M_WAVES) void rx_kernel_mixed(R
     __builtin_amdgcn_wave_barrier();
     const bool stage = !(a.tune & 2u);
     const bool scatter = GATHER && a.perm;
-    if (dc.idx != 0xffffffffu && !(kDiag && (a.tune & 16u))) {
+    if (dc.idx != 0xffffffffu) {
       const int m = (int)(dc.base & 15);
       uint32_t my_sum = *(const LDS_AS uint32_t *)(wimg + lane * IMG_STRIDE + M_SUM);
       const int nch = (m + (int)dc.len + 15) >> 4;
@@ -1396,7 +1340,7 @@ __global__ __launch_bounds__(WAVE * WPB, PPTK_RX_M_WAVES) void rx_kernel_mixed(R
         a.txside[dc.idx] = o.tx;
       emit_record(a, o, dc.idx, (LDS_AS u32x4 *)wimg + lane * 5, stage);
     }
-    if (stage && !(kDiag && (a.tune & 8u)) && (a.recs || a.recs32))
+    if (stage && (a.recs || a.recs32))
       flush_records(a, wimg, tile, lane, dc.idx, scatter);
     tile += step;
     dc = dn;
@@ -1418,7 +1362,7 @@ __global__ __launch_bounds__(WAVE * WPB, PPTK_RX_M_WAVES) void rx_kernel_mixed(R
 // turn, so no in-flight load destination is ever copied).
 constexpr int LSLOT = 80;   // LDS bytes per lane: 64-byte frame image, then the record
 
-// Coalesced tiles (PPTK_RX_LANE_COAL): when the frames are packed at a
+// Coalesced tiles: when the frames are packed at a
 // 64-byte stride and every frame spans four chunks, the tile is one
 // contiguous 4 KB run and load s of lane q takes its chunk 64 s + q (each
 // instruction reads 1 KB contiguously, as the speed-of-light kernel does,
@@ -1466,7 +1410,7 @@ __device__ __forceinline__ void lane_tile(const RxKArgs &a, uint64_t tile, int l
   LDS_AS uint8_t *slot = wimg + lane * LSLOT;
   u32x4 c[4] = {cl[0], cl[1], cl[2], cl[3]};
   if (coal) lane_chunks(wimg, lane, c);
-  if (i < a.n && !(kDiag && (a.tune & 16u))) {
+  if (i < a.n) {
     const uint32_t len = a.fixed_len;
     uint32_t d[16];
 #pragma unroll
@@ -1491,21 +1435,13 @@ __device__ __forceinline__ void lane_tile(const RxKArgs &a, uint64_t tile, int l
     }
     emit_record(a, o, (uint32_t)i, (LDS_AS u32x4 *)slot, true);
   }
-  if (!(kDiag && (a.tune & 8u)) && (a.recs || a.recs32))
+  if (a.recs || a.recs32)
     flush_records(a, wimg, tile, lane, 0u, false);
 }
 
-// (A/B: PPTK_RX_LANE_WAVES waves per SIMD the registers must allow;
-// PPTK_RX_LANE_PREFETCH 0 loads each tile at its start instead of one tile
-// ahead, for more waves in the same registers)
-#ifndef PPTK_RX_LANE_WAVES
-#define PPTK_RX_LANE_WAVES 4
-#endif
-#ifndef PPTK_RX_LANE_PREFETCH
-#define PPTK_RX_LANE_PREFETCH 1
-#endif
+// (the registers must allow four waves per SIMD)
 template <bool NT>
-__global__ __launch_bounds__(WAVE * WPB, PPTK_RX_LANE_WAVES) void rx_kernel_lane(RxKArgs a) {
+__global__ __launch_bounds__(WAVE * WPB, 4) void rx_kernel_lane(RxKArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[WPB * WAVE * LSLOT];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wv = threadIdx.x / WAVE;
@@ -1517,7 +1453,6 @@ __global__ __launch_bounds__(WAVE * WPB, PPTK_RX_LANE_WAVES) void rx_kernel_lane
   // (uniform: the batch is one contiguous run of 64-byte frame slots)
   const bool coal = lane_coalesced(a.stride, a.fixed_len);
   uint64_t tile = tr.first;
-#if PPTK_RX_LANE_PREFETCH
   u32x4 c0[4], c1[4];
   lane_load<NT>(a, pf_tile(tr, ntiles, tile), lane, nch, coal, c0);
   while (tile < tr.end) {
@@ -1527,14 +1462,6 @@ __global__ __launch_bounds__(WAVE * WPB, PPTK_RX_LANE_WAVES) void rx_kernel_lane
 #pragma unroll
     for (int s = 0; s < 4; ++s) c0[s] = c1[s];
   }
-#else
-  while (tile < tr.end) {
-    u32x4 c0[4];
-    lane_load<NT>(a, tile, lane, nch, coal, c0);
-    lane_tile<NT>(a, tile, lane, nch, coal, c0, wimg);
-    tile += step;
-  }
-#endif
 }
 
 // Descriptor sources of an offset-described (GATHER) launch: absent arrays

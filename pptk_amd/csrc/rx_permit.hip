@@ -472,10 +472,7 @@ constexpr uint32_t FHASH_PASS = 2048;     // phase 3: candidates per hash-table 
 constexpr uint32_t FHASH_MAXP = 32;       // hash-table passes at most
 constexpr uint32_t FHASH_K = 64;          // frames of one ranked bucket at most, hash path
 constexpr uint64_t FUSED_SPIN_TICKS = 200000000ull;   // 2 s of the 100 MHz clock
-#ifndef PPTK_PERMIT_CODE_REPL
-#define PPTK_PERMIT_CODE_REPL 1
-#endif
-constexpr uint32_t FCREPL = PPTK_PERMIT_CODE_REPL;   // copies of the code array (A/B)
+constexpr uint32_t FCREPL = 1;   // copies of the code array
 
 struct PermitFused {
   uint32_t *table;   // nblk rows x nwords u32 (4 u8 counts each)
@@ -849,9 +846,6 @@ __global__ __launch_bounds__(FT) void permit_fused(PermitArgs a, PermitFused f) 
     }
   };
   FSTAMP(2);
-#ifdef PPTK_PERMIT_SPEC_EARLY   // (A/B: the speculative verdicts before the table loads)
-  put_spec();
-#endif
   fused_stall(f, c, 1);
   if (fused_barrier(f, c, 1) < 0) {   // aborted: no token touched, subjects denied
     put_fail();
@@ -1013,9 +1007,7 @@ __global__ __launch_bounds__(FT) void permit_fused(PermitArgs a, PermitFused f) 
     // the speculative verdicts, after the table loads (issued ahead of them
     // they would hold up their first use: loads and stores share one
     // in-order memory counter); they drain into the barrier
-#ifndef PPTK_PERMIT_SPEC_EARLY
     put_spec();
-#endif
   }
   FSTAMP(4);
   __syncthreads();
@@ -1057,11 +1049,7 @@ __global__ __launch_bounds__(FT) void permit_fused(PermitArgs a, PermitFused f) 
   uint16_t *const tab16s = (uint16_t *)tab;
   constexpr int SW = HMAX / 2 / FT;   // code words per thread (at most)
   uint32_t cw[SW];                    // all loads in flight at once
-#ifdef PPTK_PERMIT_CODE_ROT
-  const uint32_t crot = (c >> 3) & (SW - 1);
-#else
   const uint32_t crot = 0;
-#endif
   auto wof = [&](int j) { return (((uint32_t)j + crot) & (SW - 1)) * FT + tid; };
   const uint32_t *const code_r = f.code + (c % FCREPL) * ((words + 63u) & ~63u);
 #pragma unroll
@@ -1402,9 +1390,7 @@ __global__ __launch_bounds__(FT) void permit_fused(PermitArgs a, PermitFused f) 
   const bool aligned = valigned;
 #pragma unroll
   for (int v = 0; v < FKV; ++v) {
-#ifndef PPTK_PERMIT_VERDICT_FREE
     __builtin_amdgcn_sched_barrier(0);
-#endif
     const uint32_t rel = (uint32_t)v * FT * 4 + 4 * tid;
     if (rel >= nrel) break;
     uint32_t vd[4];
@@ -1719,10 +1705,6 @@ void note_launch(const void *scratch, uint64_t k) {
 // every fused launch (hipExtLaunchKernelGGL's own, 2.2 us per call), so a
 // launch from a new stream only waits for that event -- never for the whole
 // device, which would also wait for other streams' gathers and batches.
-// (A/B builds: PPTK_PERMIT_ORDER=0, no order)
-#ifndef PPTK_PERMIT_ORDER
-#define PPTK_PERMIT_ORDER 1
-#endif
 struct FusedOrder {
   std::mutex mu;
   hipEvent_t ev = nullptr;
@@ -1811,20 +1793,16 @@ hipError_t launch_permit(const PermitArgs &a, void *scratch, hipStream_t st) {
                                                     hipEventDisableSystemFence) != hipSuccess &&
         (e = hipEventCreateWithFlags(&o.ev, hipEventDisableTiming)) != hipSuccess)
       return e;
-    if (PPTK_PERMIT_ORDER && o.any && o.last != st &&
+    if (o.any && o.last != st &&
         (e = hipStreamWaitEvent(st, o.ev, 0)) != hipSuccess)
       return e;
     const uint64_t k = g_nonce_ctr.fetch_add(1);
     f.nonce = nonce_of(k);
     note_launch(scratch, k);
-    if (PPTK_PERMIT_ORDER) {
-      // the order event as the launch's own stop event (2.2 us per call;
-      // a separate hipEventRecord behind the kernel cost 3.6)
-      hipExtLaunchKernelGGL(permit_fused<true>, dim3(g.nblk), dim3(FT), 0, st, nullptr, o.ev, 0,
-                            a, f);
-    } else {
-      hipLaunchKernelGGL(permit_fused<true>, dim3(g.nblk), dim3(FT), 0, st, a, f);
-    }
+    // the order event as the launch's own stop event (2.2 us per call;
+    // a separate hipEventRecord behind the kernel cost 3.6)
+    hipExtLaunchKernelGGL(permit_fused<true>, dim3(g.nblk), dim3(FT), 0, st, nullptr, o.ev, 0, a,
+                          f);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     o.last = st;
     o.any = true;

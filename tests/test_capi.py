@@ -726,6 +726,57 @@ def test_comm_config_caps_channels_only_when_split():
                        "pptk_rx_test_comm_config")
 
 
+PRODUCT_ENV = {"PPTK_RX_VARIANT", "PPTK_RX_TUNE", "PPTK_RX_DIRECT_MAX_BYTES",
+               "PPTK_RX_SYNC_SLOTS", "PPTK_RX_RING_DMA_PCT"}
+HOOKS_ENV = {"PPTK_RX_COMM_TEST_WARMUP_STALL_MS"} | {
+    "PPTK_RX_TEST_PERMIT_" + s for s in ("STALL_US", "STALL_MS", "STALL_AT", "SPIN_US", "SPIN_MS")}
+BUILD_SWITCHES = {"__cplusplus", "PPTK_RX_TEST_HOOKS", "PPTK_FLOW_TEAM", "PPTK_TUN_TEAM",
+                  "PPTK_FLOWSTAT_DIRECT"}
+
+
+def test_only_the_documented_switches_and_environment_names(lib):
+    """The product sources carry no build-time switch but the test hooks and
+    the documented A/B baselines, and read no environment
+    variable but the five of INTEGRATION.md section 6 (the test library: plus
+    the fault-injection knobs, named only under PPTK_RX_TEST_HOOKS); the
+    built product library holds exactly those five names."""
+    csrc = os.path.join(ROOT, "pptk_amd", "csrc")
+    tested, env = set(), {}          # env: name -> it is named only under the hooks switch
+    nfiles = 0
+    for path in glob.glob(os.path.join(csrc, "**", "*.*"), recursive=True):
+        nfiles += 1
+        arms = []                    # the open conditionals: [switch, in its first arm]
+        for line in open(path):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b(.*)", line)
+            if m:
+                d, rest = m.group(1), re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+                ids = set(re.findall(r"[A-Za-z_]\w*", rest)) - {"defined"}
+                if d in ("if", "ifdef", "ifndef"):
+                    arms.append([rest.strip(), d == "ifdef"])
+                elif d in ("elif", "else"):
+                    arms[-1][1] = False
+                else:
+                    arms.pop()
+                if d not in ("else", "endif"):
+                    tested |= ids
+                continue
+            hooked = ["PPTK_RX_TEST_HOOKS", True] in arms
+            # (rx_permit.hip's hooks read theirs through a local `knob`)
+            for name in re.findall(r"\b(?:getenv|env_long|knob)\(\s*\"([^\"]*)\"", line):
+                env[name] = env.get(name, True) and hooked
+            # any other argument: the `name` parameter of env_long and of `knob`
+            assert set(re.findall(r"\bgetenv\(\s*([A-Za-z_]\w*)", line)) <= {"name"}, (path, line)
+        assert not arms, path
+    assert nfiles > 20
+    guards = {t for t in tested if re.fullmatch(r"PPTK_\w+_H", t)}
+    assert tested - guards <= BUILD_SWITCHES, sorted(tested - guards - BUILD_SWITCHES)
+    assert set(env) == PRODUCT_ENV | HOOKS_ENV, sorted(set(env) ^ (PRODUCT_ENV | HOOKS_ENV))
+    assert {n for n, hooked in env.items() if hooked} == HOOKS_ENV
+    blob = open(os.path.join(ROOT, "pptk_amd", "libpptkrx.so"), "rb").read()
+    names = set(re.findall(rb"(?<![A-Za-z0-9_])(PPTK_[A-Z0-9_]+)\x00", blob))
+    assert names == {n.encode() for n in PRODUCT_ENV}, sorted(names)
+
+
 def test_abi_revision_matches_header(lib):
     """pptk_rx_abi() == the header's PPTK_RX_ABI == the Python binding's:
     a caller can detect a library whose structs differ from its header."""

@@ -16,7 +16,7 @@ def constants():
     src = open(os.path.join(os.path.dirname(os.path.dirname(__file__)), SRC)).read()
     m_s = int(re.search(r"constexpr int M_S = (\d+);", src).group(1))
     rmax = int(re.search(r"constexpr int M_RMAX = (\d+);", src).group(1))
-    m_d = int(re.search(r"#define PPTK_RX_M_D (\d+)", src).group(1))
+    m_d = int(re.search(r"constexpr int M_D = (\d+);", src).group(1))
     return m_s, rmax, m_d
 
 
