@@ -15,11 +15,11 @@ HIP_SRCS := pptk_amd/csrc/rx_kernel.hip pptk_amd/csrc/rx_bin.hip pptk_amd/csrc/r
             pptk_amd/csrc/rx_capi.hip pptk_amd/csrc/rx_comm.hip pptk_amd/csrc/rx_ring.hip \
             pptk_amd/csrc/tx_frag.hip pptk_amd/csrc/tx_tunnel.hip pptk_amd/csrc/tx_hdr.hip \
             pptk_amd/csrc/rx_flow.hip pptk_amd/csrc/rx_flowstat.hip pptk_amd/csrc/rx_flowlearn.hip \
-            pptk_amd/csrc/rx_host.hip
+            pptk_amd/csrc/rx_host.hip pptk_amd/csrc/ip_reass.hip
 C_SRCS := pptk_amd/csrc/host/ipcksum.c pptk_amd/csrc/host/hashseed.c pptk_amd/csrc/host/tcpopt.c \
           pptk_amd/csrc/host/iphash.c pptk_amd/csrc/host/timerlink.c pptk_amd/csrc/host/ipfrag.c \
           pptk_amd/csrc/host/tcpseq.c pptk_amd/csrc/host/tunnel.c pptk_amd/csrc/host/flowtab.c \
-          pptk_amd/csrc/host/flowlearn.c
+          pptk_amd/csrc/host/flowlearn.c pptk_amd/csrc/host/ipreass.c
 HDRS := $(wildcard include/*.h) pptk_amd/csrc/rx_internal.h pptk_amd/csrc/copy16.h \
         pptk_amd/csrc/frame_view.h pptk_amd/csrc/flowtab.h pptk_amd/csrc/host_plan.h
 HIP_OBJS := $(patsubst pptk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))

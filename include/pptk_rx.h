@@ -590,6 +590,151 @@ int pptk_ip_fragment_host(const void *frame, uint32_t len, uint32_t mtu, uint8_t
                           uint64_t out_stride, uint32_t out_cap, uint16_t *out_len,
                           uint8_t *status);
 
+/* IPv4 reassembly, the receiving half of the reference's ipfrag/
+ * (ipfrag/ipreass.c reassctx_add / reassctx_reassemble) as a stateless,
+ * batch-local call: it rebuilds the datagrams whose fragments are all in the
+ * batch and reports the rest.  The loop is
+ *   pptk_rx_batch_device (d_recs + d_frag) -> pptk_ip_reass_device
+ *      -> pptk_rx_batch_device on the slots -> pptk_tunnel_decap_device ...
+ * and carrying the members of INCOMPLETE datagrams over to the next batch is
+ * the caller's job, done with descriptors (keep their d_off / d_len entries
+ * and put them in front of the next batch's; the frames stay where they
+ * are).  pptk_ip_reass_host (pptk_amd/csrc/host/ipreass.c, plain C over
+ * iphdr.h / ipcksum.h) is the statement of this contract; the device call
+ * equals it byte for byte, in every output array and in every byte it must
+ * not touch.
+ *
+ * Inputs.  Frame layout and read bounds are those of pptk_ip_fragment_device;
+ * recs[i] and frag[i] are what pptk_rx_batch_device wrote for the same
+ * frames.  The records are trusted for meaning, never for memory safety:
+ * whatever they say, no byte outside a frame's own 16-byte chunks is read and
+ * nothing outside the output arrays is written.
+ *
+ * Per frame (fstatus[i], dgram[i]).  Frame i is a fragment
+ * (PPTK_REASS_FST_FRAG) when recs[i].flags has PARSED and FRAGMENT and has
+ * neither MALFORMED nor IPV6; every other frame gets status 0 and dgram[i] =
+ * 0xffffffff.  With l3 = recs[i].l3_off, off = frag[i].frag_off, dl =
+ * frag[i].data_len, MF = frag[i].flags & PPTK_RX_FRAG_MF and ihl_i = 4 *
+ * (frame[l3] & 15), a fragment is rejected (dgram[i] = 0xffffffff) with
+ *   PPTK_REASS_FST_BADCKSUM  recs[i].ip_cksum != 0
+ *   PPTK_REASS_FST_BADFRAG   l3 is not 14 or 18; len <= l3 (then frame[l3] is
+ *                            not read); ihl_i < 20; dl == 0; off + dl > 65535
+ *                            (ipreass.c:119-122); MF and dl % 8 != 0; l3 +
+ *                            ihl_i + dl > len
+ * (both bits when both hold).  The remaining fragments are the candidates,
+ * numbered in index order; only the first max_candidates are considered, the
+ * rest get PPTK_REASS_FST_SKIPPED (dgram[i] = 0xffffffff) and count in
+ * hdr.candidates and nowhere else, which bounds work and scratch under a
+ * flood.  A considered candidate gets PPTK_REASS_FST_MEMBER and dgram[i] =
+ * its datagram's report index, and PPTK_REASS_FST_DONE too when that datagram
+ * is WRITTEN: the frame is consumed.
+ *
+ * Datagrams.  The key is (src[0..3], dst[0..3], proto of the record, ident &
+ * 0xffff), compared exactly (a hash only finds the bucket); L2 is not part of
+ * it.  The leader is the key's lowest-indexed considered candidate; report
+ * entries are the datagrams in ascending leader index, entry k written only
+ * when k < report_cap.  Order a datagram's members by (off, frame index);
+ * its status is the first that applies of
+ *   PPTK_REASS_DG_TOOMANY     more than 64 members (nothing else is examined)
+ *   PPTK_REASS_DG_OVERLAP     two neighbours with off[k] + dl[k] > off[k+1];
+ *                             more than one member without MF; a member
+ *                             without MF that is not the last in this order
+ *   PPTK_REASS_DG_INCOMPLETE  no member without MF; off[0] != 0; a gap
+ *                             between neighbours
+ *   PPTK_REASS_DG_COMPLETE    otherwise; total = off[last] + dl[last]
+ * For a COMPLETE datagram l2 is the leader's l3 and ihl the leader's ihl_i
+ * (the reference takes the header of the first packet added, ipreass.c:47-50),
+ * len = l2 + ihl + total, and it also gets, the first that applies of
+ *   PPTK_REASS_DG_TOOBIG   len > 65535 (lengths are 16 bits here, as d_len;
+ *                          this includes ihl + total > 65535) or
+ *                          round_up(len, 16) > out_stride
+ *   PPTK_REASS_DG_NOROOM   the datagram takes the next slot in report order
+ *                          (TOOBIG ones take none) and that slot is >= out_cap
+ *   PPTK_REASS_DG_WRITTEN  otherwise
+ * A written slot is what reassctx_reassemble writes (ipreass.c:61-86): the
+ * leader's first l2 + ihl bytes, ip_set_frag_off(0) and ip_set_more_frags(0)
+ * (the DF and reserved bits stay), ip_set_total_len(ihl + total),
+ * ip_set_hdr_cksum_calc(ip, ihl), then each member's dl payload bytes from
+ * frame + l3 + ihl_i at l2 + ihl + off.  Bytes [len, round_up(len, 16)) are
+ * zero, the rest of the slot is untouched, out_len[slot] = len.  The slots go
+ * straight back into pptk_rx_batch_device (stride = out_stride, d_len =
+ * d_out_len) and pptk_tunnel_decap_device.
+ *
+ * Deviation from the reference, stated: it accepts overlapping fragments
+ * (the later copy wins, the smallest last end is taken); here such a datagram
+ * is reported as OVERLAP and not built, as current IP stacks do, and the
+ * host decides (dropping is the sane policy).
+ *
+ * -EINVAL: a null ctx (device call) or hdr; with n > 0 a null frames, recs,
+ * frag, dgram or fstatus, a scratch (device call) that is null, not 256-byte
+ * aligned or below pptk_ip_reass_scratch_bytes(n, max_candidates), no layout
+ * (no off, stride 0, n > 1) or a fixed_len above 65535 without len; a null out
+ * or out_len with out_cap > 0, a null report with report_cap > 0; out not
+ * 16-byte, recs or frag not 16-byte (device call), report or dgram not 4-byte,
+ * hdr not 8-byte aligned; out_stride not a multiple of 16; n > 2^24;
+ * max_candidates 0 or above 2^24; out_cap or report_cap >= 2^32.  n = 0
+ * writes a zero header and nothing else.  The host call returns -ENOMEM when
+ * its tables cannot be allocated.
+ *
+ * The device call is asynchronous on `stream`: a fixed sequence of launches
+ * ordered by kernel boundaries only (no grid barrier, no spin, no lane waits
+ * for another workgroup's store), every loop bound a kernel argument or a
+ * device value clamped by one, all arithmetic integer, the result the same
+ * for any grid and interleaving.  It clears what it needs of the scratch and
+ * must not share a scratch with a call in flight on another stream.
+ * pptk_ip_reass_shape reports the member limit (64) and the frames of one
+ * workgroup of the per-frame passes; results do not depend on the latter.
+ *
+ * Out of scope: IPv6 fragments, pptk_rx_rec32 input, state across batches
+ * and timeouts, datagrams of more than 64 fragments, and merging overlaps. */
+#define PPTK_REASS_FST_FRAG 0x01u      /* PARSED | FRAGMENT IPv4, not MALFORMED   */
+#define PPTK_REASS_FST_BADCKSUM 0x02u  /* rejected: bad header checksum           */
+#define PPTK_REASS_FST_BADFRAG 0x04u   /* rejected: inconsistent fragment fields  */
+#define PPTK_REASS_FST_SKIPPED 0x08u   /* a candidate past max_candidates         */
+#define PPTK_REASS_FST_MEMBER 0x10u    /* considered: dgram[i] is its datagram    */
+#define PPTK_REASS_FST_DONE 0x20u      /* its datagram was WRITTEN: consumed      */
+#define PPTK_REASS_DG_COMPLETE 0x01u   /* every byte of the datagram is there     */
+#define PPTK_REASS_DG_WRITTEN 0x02u    /* COMPLETE and built in `slot`            */
+#define PPTK_REASS_DG_INCOMPLETE 0x04u /* a hole, or the last fragment is missing */
+#define PPTK_REASS_DG_OVERLAP 0x08u    /* overlapping or contradictory fragments  */
+#define PPTK_REASS_DG_TOOMANY 0x10u    /* more than 64 members                    */
+#define PPTK_REASS_DG_TOOBIG 0x20u     /* COMPLETE, does not fit a slot           */
+#define PPTK_REASS_DG_NOROOM 0x40u     /* COMPLETE, slot >= out_cap               */
+struct pptk_reass_dgram {  /* 16 bytes, one report entry per datagram */
+  uint32_t first;          /*  0 frame index of its leader                       */
+  uint32_t slot;           /*  4 output slot, 0xffffffff unless WRITTEN          */
+  uint32_t frags;          /*  8 considered fragments carrying its key           */
+  uint16_t out_len;        /* 12 l2 + ihl + total; 0 unless COMPLETE and <= 65535 */
+  uint8_t status;          /* 14 PPTK_REASS_DG_*                                 */
+  uint8_t reserved;        /* 15 always 0                                        */
+};
+struct pptk_reass_hdr {    /* 48 bytes, 8-byte aligned */
+  uint64_t candidates;     /* fragments that passed the per-frame checks         */
+  uint64_t considered;     /* min(candidates, max_candidates)                    */
+  uint64_t dgrams;         /* datagrams among the considered                     */
+  uint64_t reported;       /* min(dgrams, report_cap)                            */
+  uint64_t complete;       /* datagrams with PPTK_REASS_DG_COMPLETE              */
+  uint64_t written;        /* slots written                                      */
+};
+size_t pptk_ip_reass_scratch_bytes(uint64_t n, uint64_t max_candidates);
+int pptk_ip_reass_device(struct pptk_rx_ctx *ctx, const uint8_t *d_frames,
+                         const uint64_t *d_off, const uint16_t *d_len, uint64_t stride,
+                         uint32_t fixed_len, uint64_t n, const struct pptk_rx_rec *d_recs,
+                         const struct pptk_rx_frag *d_frag, uint64_t max_candidates,
+                         uint8_t *d_out, uint64_t out_stride, uint64_t out_cap,
+                         uint16_t *d_out_len, struct pptk_reass_dgram *d_report,
+                         uint64_t report_cap, uint32_t *d_dgram, uint8_t *d_fstatus,
+                         struct pptk_reass_hdr *d_hdr, void *d_scratch, size_t scratch_bytes,
+                         void *stream);
+int pptk_ip_reass_host(const uint8_t *frames, const uint64_t *off, const uint16_t *len,
+                       uint64_t stride, uint32_t fixed_len, uint64_t n,
+                       const struct pptk_rx_rec *recs, const struct pptk_rx_frag *frag,
+                       uint64_t max_candidates, uint8_t *out, uint64_t out_stride,
+                       uint64_t out_cap, uint16_t *out_len, struct pptk_reass_dgram *report,
+                       uint64_t report_cap, uint32_t *dgram, uint8_t *fstatus,
+                       struct pptk_reass_hdr *hdr);
+void pptk_ip_reass_shape(uint32_t *max_frags, uint32_t *block_frames);
+
 /* GRE tunnel gateway (tunnel ingress and egress), the batch form of the
  * reference's ldp/ldptunnel.c: encap puts the fixed 38-byte header Ethernet +
  * IPv4 + GRE with protocol type 0x6558 (transparent Ethernet bridging) in

@@ -46,6 +46,19 @@ SEQ_NOFLOW = 0xFFFFFFFF   # d_idx entry meaning "no flow"
 # PPTK_FRAG_ST_*: per-frame status of pptk_ip_fragment_device / _host
 (FRAG_ST_IPV4, FRAG_ST_FITS, FRAG_ST_DONE, FRAG_ST_DF, FRAG_ST_ISFRAG, FRAG_ST_BADCKSUM,
  FRAG_ST_NOROOM) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
+# pptk_ip_reass_device / _host: per-frame status bits, per-datagram status bits,
+# struct pptk_reass_dgram (one report entry) and struct pptk_reass_hdr
+(REASS_FST_FRAG, REASS_FST_BADCKSUM, REASS_FST_BADFRAG, REASS_FST_SKIPPED, REASS_FST_MEMBER,
+ REASS_FST_DONE) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+(REASS_DG_COMPLETE, REASS_DG_WRITTEN, REASS_DG_INCOMPLETE, REASS_DG_OVERLAP, REASS_DG_TOOMANY,
+ REASS_DG_TOOBIG, REASS_DG_NOROOM) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
+REASS_NONE, REASS_MAX_FRAGS = 0xFFFFFFFF, 64
+REASS_DGRAM_DTYPE = np.dtype([("first", "<u4"), ("slot", "<u4"), ("frags", "<u4"),
+                              ("out_len", "<u2"), ("status", "u1"), ("reserved", "u1")])
+assert REASS_DGRAM_DTYPE.itemsize == 16
+REASS_HDR_DTYPE = np.dtype([("candidates", "<u8"), ("considered", "<u8"), ("dgrams", "<u8"),
+                            ("reported", "<u8"), ("complete", "<u8"), ("written", "<u8")])
+assert REASS_HDR_DTYPE.itemsize == 48
 # struct pptk_tunnel and the status bits of pptk_tunnel_encap_* / _decap_*
 TUNNEL_DTYPE = np.dtype([("eth_dst", "u1", 6), ("eth_src", "u1", 6), ("src", "<u4"),
                          ("dst", "<u4"), ("id", "<u2"), ("ttl", "u1"), ("tos", "u1"),

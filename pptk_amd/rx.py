@@ -214,6 +214,13 @@ _SIGNATURES = {
     "pptk_ip_fragment_device": (ci, (vp, vp, vp, vp, u64, u32, u64, u32, vp, u64, u64)
                                 + (vp,) * 8),
     "pptk_ip_fragment_host": (ci, (vp, u32, u32, vp, u64, u32, vp, vp)),
+    # IPv4 reassembly
+    "pptk_ip_reass_scratch_bytes": (sz, (u64, u64)),
+    "pptk_ip_reass_device": (ci, (vp, vp, vp, vp, u64, u32, u64, vp, vp, u64, vp, u64, u64, vp, vp,
+                                  u64, vp, vp, vp, vp, sz, vp)),
+    "pptk_ip_reass_host": (ci, (vp, vp, vp, u64, u32, u64, vp, vp, u64, vp, u64, u64, vp, vp, u64,
+                                vp, vp, vp)),
+    "pptk_ip_reass_shape": (None, (P(u32), P(u32))),
     # GRE tunnel
     "pptk_tunnel_encap_device": (ci, (vp, vp, vp, vp, u64, u32, u64, vp, u64, vp, u32, vp, u64,
                                       vp, vp, vp)),
@@ -681,6 +688,50 @@ class RxContext:
                "pptk_ip_fragment_device")
         return dict(out=out, out_stride=out_stride, out_len=out_len, out_src=out_src, first=first,
                     count=count, status=status, totals=totals, scratch=scratch)
+
+    def ip_reass_device(self, frames, n, recs, frag, max_candidates, out_cap, out_stride,
+                        report_cap=None, off=None, lens=None, stride=0, fixed_len=0, out=None,
+                        out_len=None, report=None, dgram=None, fstatus=None, hdr=None,
+                        scratch=None, stream=None):
+        """Batch-local IPv4 reassembly (pptk_ip_reass_device), asynchronous.
+        recs / frag: the uint8 CUDA tensors of 64-byte records and 16-byte
+        fragment side records batch_device wrote for the same frames.
+        Allocates what is not given -- out ((out_cap, out_stride) uint8),
+        out_len (int16, the C array's uint16 bits), report (uint8, report_cap
+        entries of records.REASS_DGRAM_DTYPE; report_cap = n unless given),
+        dgram (int32, n), fstatus (uint8, n), hdr (int64, the six words of
+        records.REASS_HDR_DTYPE) and the scratch -- and returns them as a
+        dict.  Download hdr, then hdr.written slots and hdr.reported
+        entries."""
+        dev = frames.device
+        report_cap = n if report_cap is None else report_cap
+        out = _empty(out, (max(out_cap, 1), out_stride), "uint8", dev)
+        out_len = _empty(out_len, max(out_cap, 1), "int16", dev)
+        report = _empty(report, max(report_cap, 1) * 16, "uint8", dev)
+        dgram = _empty(dgram, max(n, 1), "int32", dev)
+        fstatus = _empty(fstatus, max(n, 1), "uint8", dev)
+        hdr = _empty(hdr, 6, "int64", dev)
+        need = self._L.pptk_ip_reass_scratch_bytes(n, max_candidates)
+        scratch = _empty(scratch, max(need, 256), "uint8", dev)
+        _check(self._L.pptk_ip_reass_device(self._ctx, _dp(frames), _dp(off), _dp(lens), stride,
+                                            fixed_len, n, _dp(recs), _dp(frag), max_candidates,
+                                            _dp(out), out_stride, out_cap, _dp(out_len),
+                                            _dp(report), report_cap, _dp(dgram), _dp(fstatus),
+                                            _dp(hdr), _dp(scratch),
+                                            scratch.numel() * scratch.element_size(),
+                                            _stream(stream, dev)), "pptk_ip_reass_device")
+        return dict(out=out, out_stride=out_stride, out_len=out_len, report=report, dgram=dgram,
+                    fstatus=fstatus, hdr=hdr, scratch=scratch)
+
+    def ip_reass_host(self, *args, **kw):
+        """pptk_ip_reass_host (the module's ip_reass_host) with this context's library."""
+        return ip_reass_host(*args, lib_path=self._L._name, **kw)
+
+    def ip_reass_scratch_bytes(self, n, max_candidates):
+        return self._L.pptk_ip_reass_scratch_bytes(n, max_candidates)
+
+    def ip_reass_shape(self):
+        return ip_reass_shape(lib_path=self._L._name)
 
     def tunnel_encap_device(self, frames, n, tun, idx=None, id_base=0, off=None, lens=None,
                             stride=0, fixed_len=0, out=None, out_stride=0, out_len=None,
@@ -1175,6 +1226,62 @@ def ip_fragment_host(frame, mtu, out_cap, out_stride=0, lib_path=None):
         bytes(frame), len(frame), mtu, out.ctypes.data, out_stride, out_cap, out_len.ctypes.data,
         ctypes.byref(status)), "pptk_ip_fragment_host", True)
     return rc, status.value, out[:out_cap], out_len[:out_cap]
+
+
+def ip_reass_host(buf, recs, frag, max_candidates, out_cap, out_stride, report_cap=None, off=None,
+                  lens=None, stride=0, fixed_len=0, n=None, fill=0xEE, lib_path=None):
+    """pptk_ip_reass_host, the CPU statement of ip_reass_device, over NumPy
+    arrays: buf the frame bytes, recs / frag the records (records.REC_DTYPE /
+    FRAG_DTYPE or their bytes), off (uint64) / lens (uint16) or stride /
+    fixed_len the layout.  Every output array is pre-filled with `fill` so a
+    caller can see what was not touched.  Returns dict(hdr, out, out_len,
+    report, dgram, fstatus): hdr one records.REASS_HDR_DTYPE entry, out
+    (out_cap, out_stride) uint8, report report_cap REASS_DGRAM_DTYPE
+    entries (report_cap = n unless given)."""
+    from .records import REASS_DGRAM_DTYPE, REASS_HDR_DTYPE
+    b = np.ascontiguousarray(buf, dtype=np.uint8)
+    r = np.ascontiguousarray(recs).view(np.uint8).reshape(-1)
+    f = np.ascontiguousarray(frag).view(np.uint8).reshape(-1)
+    if n is None:
+        n = r.size // 64
+    if r.size < n * 64 or f.size < n * 16:
+        raise ValueError("ip_reass_host: n 64-byte records and n 16-byte side records")
+    report_cap = n if report_cap is None else report_cap
+    o = None if off is None else np.ascontiguousarray(off, dtype=np.uint64)
+    ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint16)
+    out = _aligned_bytes(max(out_cap, 1) * out_stride)
+    out[:] = fill
+    out_len = np.full(max(out_cap, 1), fill * 0x0101, np.uint16)
+    report = np.full(max(report_cap, 1) * 16, fill, np.uint8)
+    dgram = np.full(max(n, 1), fill * 0x01010101, np.uint32)
+    fstatus = np.full(max(n, 1), fill, np.uint8)
+    hdr = np.zeros(1, REASS_HDR_DTYPE)
+
+    def p(a):
+        return None if a is None else a.ctypes.data
+
+    _check(lib(lib_path).pptk_ip_reass_host(
+        p(b), p(o), p(ln), stride, fixed_len, n, p(r), p(f), max_candidates,
+        p(out) if out_cap else None, out_stride, out_cap, p(out_len) if out_cap else None,
+        p(report) if report_cap else None, report_cap, p(dgram), p(fstatus), p(hdr)),
+        "pptk_ip_reass_host")
+    return dict(hdr=hdr[0], out=out[:out_cap * out_stride].reshape(out_cap, out_stride),
+                out_len=out_len[:out_cap], report=report[:report_cap * 16].view(REASS_DGRAM_DTYPE),
+                dgram=dgram[:n], fstatus=fstatus[:n])
+
+
+def ip_reass_scratch_bytes(n, max_candidates, lib_path=None):
+    """pptk_ip_reass_scratch_bytes: the device scratch a reassembly call over
+    n frames with this max_candidates needs (0 for n = 0)."""
+    return lib(lib_path).pptk_ip_reass_scratch_bytes(n, max_candidates)
+
+
+def ip_reass_shape(lib_path=None):
+    """pptk_ip_reass_shape: (max_frags, block_frames) of the library's
+    reassembly kernels."""
+    m, b = ctypes.c_uint32(), ctypes.c_uint32()
+    lib(lib_path).pptk_ip_reass_shape(ctypes.byref(m), ctypes.byref(b))
+    return m.value, b.value
 
 
 def tunnel_encap_host(frame, tun, seq=0, out_cap=None, lib_path=None):
