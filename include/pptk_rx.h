@@ -1156,6 +1156,123 @@ int pptk_flow_learn_host(const struct pptk_rx_rec *recs, const uint8_t *status, 
                          struct pptk_flow_learn_hdr *hdr);
 void pptk_flow_learn_shape(uint32_t *block_frames, uint32_t *scan_width);
 
+/* Egress dispatch: per-port tx lists from a batch in device memory.  Every
+ * stage above ends with per-frame results in frame order; a forwarder finally
+ * needs which frames leave through which port.  The reference ends its loop
+ * with that step -- ldp/ldpswitch.c:276-318 appends a packet to the output
+ * table of its port for a known destination, to every port's but the ingress
+ * port's for an unknown one (:296-305), then calls ldp_out_inject once per port
+ * (:311-318); ldpfwd.c and ldptunnel.c do the two-port form.  Here one call
+ * turns a per-frame port code, or the flow index of pptk_flow_lookup_device
+ * and a code per flow value, into one packed list of frame indices (and,
+ * where asked for, their offsets and lengths) with a run per port:
+ *   rx -> pptk_flow_lookup_device -> pptk_tx_dispatch_device(idx, flow_port,
+ *      miss_code = PPTK_PORT_FLOOD) -> download ports -> per port p: inject
+ *      out_off / out_len[start .. start + count).
+ *
+ * pptk_tx_dispatch_host is the CPU statement; the device call equals it byte
+ * for byte.  Frame i is classified in this order.  (1) subject given and
+ * subject[i] == 0: dropped.  (2) Its code: port[i] with `port` set; with
+ * `idx` set miss_code where idx[i] == PPTK_FLOW_NONE, otherwise the frame is
+ * bad where idx[i] >= flows (flow_port is not read for it), otherwise
+ * flow_port[idx[i]].  (3) A code below nports is unicast to that port -- also
+ * when that port is the frame's ingress port, as in the reference; such a
+ * frame counts in hdr.hairpin.  PPTK_PORT_FLOOD makes a flood frame,
+ * PPTK_PORT_DROP drops, any other code makes the frame bad.  Bad frames go
+ * nowhere and count in hdr.bad, not in hdr.dropped.  The ingress port of
+ * frame i is in_port ? in_port[i] : in_port_all; a value at or above nports
+ * means "none", and a flood then reaches all nports ports.
+ *
+ * Port p's run is every i, ascending, that is unicast to p or is a flood
+ * frame whose ingress port is not p: the order in which the reference's loop
+ * fills port p's output table.  The runs lie back to back in port order:
+ * ports[0].start == 0, ports[p + 1].start == ports[p].start + ports[p].count.
+ * Entry g of the packed list is written only for g < cap: list[g] = i,
+ * out_off[g] = off ? off[i] : i * stride, out_len[g] = len ? len[i] :
+ * fixed_len (its low 16 bits).  With a cap below hdr.total every port before
+ * the cut is complete and the cut port holds a prefix of its run; ports and
+ * hdr are always complete, and `bytes` sums the frame lengths (len[i] or
+ * fixed_len) of the whole run whatever cap is.  Nothing is written outside
+ * the arrays or past `written`.  cap == 0 with a null list is legal, the call
+ * then only counts; out_off and out_len are nullable.  n == 0 writes a zero
+ * header and nports zero entries and launches no more than that.  A flood
+ * with nports == 1 from port 0 reaches nobody and still counts in hdr.flood.
+ * The padding members are ignored.
+ *
+ * -EINVAL: a null ctx (device call); a null d, ports or hdr; both or neither
+ * of port / idx set with n > 0; idx without flow_port while flows > 0; a
+ * miss_code that is not below nports, FLOOD or DROP; nports 0 or above
+ * PPTK_PORT_MAX; n >= 2^32; a null list with cap > 0; idx or list not 4-byte,
+ * off, out_off, ports or hdr not 8-byte, len or out_len not 2-byte aligned
+ * (port, subject, in_port and flow_port may have any alignment); and, on the
+ * device call with n > 0, a scratch that is null, not 256-byte aligned or
+ * smaller than pptk_tx_dispatch_scratch_bytes(n, nports) (0 for n = 0 or
+ * arguments the call would reject).
+ *
+ * The device call reads `d` before it returns (the struct itself is host
+ * memory, its arrays device memory), clears what it needs of the scratch
+ * itself, is asynchronous on `stream` (at most four launches ordered by the
+ * stream alone, no host synchronisation) and must not share a scratch with a
+ * call in flight on another stream.  The order of a run never depends on the
+ * grid or on arrival: no atomic operation takes part in a position.
+ * pptk_tx_dispatch_shape reports the built kernels: the frames of one
+ * workgroup of the count and scatter passes (block_frames) and the block
+ * counts a scan workgroup takes per round (scan_width).  Results do not
+ * depend on it.
+ *
+ * Out of scope: a MAC-keyed table and MAC learning (the caller supplies the
+ * code per frame, or per flow through the 5-tuple table); copying frame bytes
+ * into per-port buffers (the lists describe frames in place); VLAN-scoped
+ * flooding or multicast groups beyond "all but ingress"; more than 64 ports;
+ * carrying the fragmenter's d_out_src through (the caller dispatches the
+ * slots as a batch of their own); a host ldp_packet[] form. */
+#define PPTK_PORT_MAX   64u
+#define PPTK_PORT_FLOOD 0xffu   /* every port but the frame's ingress port (ldpswitch.c:296-305) */
+#define PPTK_PORT_DROP  0xfeu   /* no port */
+
+struct pptk_dispatch_port {   /* 32 bytes, one per port, device memory */
+  uint64_t start;             /* first entry of this port's run in the list      */
+  uint64_t count;             /* entries of the run, whatever cap is             */
+  uint64_t bytes;             /* sum of the frame lengths of the run             */
+  uint64_t flooded;           /* entries of the run that come from flood frames  */
+};
+struct pptk_dispatch_hdr {    /* 64 bytes, 8-byte aligned */
+  uint64_t total;             /* sum of count over the ports                     */
+  uint64_t written;           /* min(total, cap)                                 */
+  uint64_t unicast, flood, dropped, bad;   /* frames by class, sum == n          */
+  uint64_t hairpin;           /* unicast frames whose port is their ingress port */
+  uint64_t reserved;          /* 0 */
+};
+struct pptk_dispatch {        /* arguments, host and device call alike; 152 bytes */
+  uint64_t n;
+  const uint8_t *port;        /* per-frame code; exactly one of port / idx set   */
+  const uint32_t *idx;        /* per-frame flow index (pptk_flow_lookup_device)  */
+  const uint8_t *flow_port;   /* with idx: code per flow value, `flows` entries  */
+  uint64_t flows;
+  const uint8_t *subject;     /* nullable; 0 = frame is dropped                  */
+  const uint8_t *in_port;     /* nullable per-frame ingress port                 */
+  uint32_t in_port_all;       /* ingress port of every frame when in_port NULL   */
+  uint32_t nports;            /* 1 .. PPTK_PORT_MAX                              */
+  uint8_t miss_code;          /* with idx: code of a PPTK_FLOW_NONE frame        */
+  uint8_t pad0[7];
+  const uint64_t *off;        /* nullable: frame i lies at i * stride            */
+  const uint16_t *len;        /* nullable: every frame is fixed_len long         */
+  uint64_t stride;
+  uint32_t fixed_len;
+  uint32_t pad1;
+  uint32_t *list;             /* frame indices, `cap` entries                    */
+  uint64_t *out_off;          /* nullable: off of list[g]'s frame                */
+  uint16_t *out_len;          /* nullable: len of list[g]'s frame                */
+  uint64_t cap;
+  struct pptk_dispatch_port *ports;   /* nports entries */
+  struct pptk_dispatch_hdr *hdr;
+};
+size_t pptk_tx_dispatch_scratch_bytes(uint64_t n, uint32_t nports);
+int pptk_tx_dispatch_device(struct pptk_rx_ctx *ctx, const struct pptk_dispatch *d,
+                            void *d_scratch, size_t scratch_bytes, void *stream);
+int pptk_tx_dispatch_host(const struct pptk_dispatch *d);
+void pptk_tx_dispatch_shape(uint32_t *block_frames, uint32_t *scan_width);
+
 /* Tuning: force kernel variant `variant` (0 .. pptk_rx_variant_count()-1)
  * and/or memory-policy flags for every later batch of this context; -1
  * restores the automatic choice (variant by frame length and alignment).

@@ -84,6 +84,15 @@ assert FLOW_STATS_DTYPE.itemsize == 32
 FLOW_LEARN_HDR_DTYPE = np.dtype([("candidates", "<u8"), ("considered", "<u8"), ("flows", "<u8"),
                                  ("written", "<u8")])
 assert FLOW_LEARN_HDR_DTYPE.itemsize == 32
+# struct pptk_dispatch_port / pptk_dispatch_hdr and the port codes
+# (include/pptk_rx.h "Egress dispatch")
+DISPATCH_PORT_DTYPE = np.dtype([("start", "<u8"), ("count", "<u8"), ("bytes", "<u8"),
+                                ("flooded", "<u8")])
+DISPATCH_HDR_DTYPE = np.dtype([("total", "<u8"), ("written", "<u8"), ("unicast", "<u8"),
+                               ("flood", "<u8"), ("dropped", "<u8"), ("bad", "<u8"),
+                               ("hairpin", "<u8"), ("reserved", "<u8")])
+assert DISPATCH_PORT_DTYPE.itemsize == 32 and DISPATCH_HDR_DTYPE.itemsize == 64
+PORT_MAX, PORT_FLOOD, PORT_DROP = 64, 0xFF, 0xFE
 
 REC32_DTYPE = np.dtype([
     ("flow_hash", "<u8"),

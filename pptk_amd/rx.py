@@ -166,7 +166,23 @@ class LdpPacket(ctypes.Structure):
                 ("ancillary64", ctypes.c_uint64)]
 
 
+class Dispatch(ctypes.Structure):
+    """struct pptk_dispatch (include/pptk_rx.h "Egress dispatch"): the
+    arguments of pptk_tx_dispatch_device / _host; the pointers are addresses."""
+    _fields_ = [("n", ctypes.c_uint64), ("port", ctypes.c_void_p), ("idx", ctypes.c_void_p),
+                ("flow_port", ctypes.c_void_p), ("flows", ctypes.c_uint64),
+                ("subject", ctypes.c_void_p), ("in_port", ctypes.c_void_p),
+                ("in_port_all", ctypes.c_uint32), ("nports", ctypes.c_uint32),
+                ("miss_code", ctypes.c_uint8), ("pad0", ctypes.c_uint8 * 7),
+                ("off", ctypes.c_void_p), ("len", ctypes.c_void_p), ("stride", ctypes.c_uint64),
+                ("fixed_len", ctypes.c_uint32), ("pad1", ctypes.c_uint32),
+                ("list", ctypes.c_void_p), ("out_off", ctypes.c_void_p),
+                ("out_len", ctypes.c_void_p), ("cap", ctypes.c_uint64),
+                ("ports", ctypes.c_void_p), ("hdr", ctypes.c_void_p)]
+
+
 assert ctypes.sizeof(LdpPacket) == 24
+assert ctypes.sizeof(Dispatch) == 152
 assert ctypes.sizeof(RxOpts) == 40
 
 # Every C function this module binds: name -> (restype, argtypes), as its
@@ -254,6 +270,11 @@ _SIGNATURES = {
     "pptk_flow_learn_device": (ci, (vp, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, sz, vp)),
     "pptk_flow_learn_host": (ci, (vp, vp, u64, u64, vp, vp, vp, u64, vp)),
     "pptk_flow_learn_shape": (None, (P(u32), P(u32))),
+    # egress dispatch
+    "pptk_tx_dispatch_scratch_bytes": (sz, (u64, u32)),
+    "pptk_tx_dispatch_device": (ci, (vp, P(Dispatch), vp, sz, vp)),
+    "pptk_tx_dispatch_host": (ci, (P(Dispatch),)),
+    "pptk_tx_dispatch_shape": (None, (P(u32), P(u32))),
     # tuning
     "pptk_rx_set_tuning": (ci, (vp, ci, ci)),
     "pptk_rx_variant_count": (ci, ()),
@@ -859,6 +880,48 @@ class RxContext:
                                               _stream(stream, dev)), "pptk_flow_learn_device")
         return dict(hdr=hdr, new_recs=new_recs, first=first, packets=packets, scratch=scratch)
 
+    def tx_dispatch_device(self, n, nports, port=None, idx=None, flow_port=None, miss_code=None,
+                           subject=None, in_port=None, in_port_all=None, off=None, lens=None,
+                           stride=0, fixed_len=0, cap=None, out_list=None, out_off=None,
+                           out_len=None, ports=None, hdr=None, scratch=None, stream=None):
+        """pptk_tx_dispatch_device, asynchronous: the per-port tx lists of n
+        frames by their code -- port (uint8 CUDA tensor), or idx (int32, the
+        index of flow_lookup_device) with flow_port (uint8, one code per flow
+        value) and miss_code (default records.PORT_DROP).  subject and in_port
+        are uint8 tensors or None; in_port_all defaults to "none".  Allocates
+        what is not given -- out_list (int32), out_off (int64) and out_len
+        (int16) of cap entries (cap defaults to n; pass False for a null
+        out_off / out_len), ports (int64, 4 words per port:
+        records.DISPATCH_PORT_DTYPE), hdr (int64, records.DISPATCH_HDR_DTYPE)
+        and the scratch (uint8, tx_dispatch_scratch_bytes(n, nports)) -- and
+        returns dict(hdr, ports, list, out_off, out_len, scratch).  Download
+        ports, then each port's entries [start, start + count) below
+        hdr.written."""
+        from .records import PORT_DROP, PORT_MAX
+        dev = (port if port is not None else idx).device
+        cap = n if cap is None else cap
+        if cap:
+            out_list = _empty(out_list, cap, "int32", dev)
+        out_off = None if out_off is False else _empty(out_off, max(cap, 1), "int64", dev)
+        out_len = None if out_len is False else _empty(out_len, max(cap, 1), "int16", dev)
+        ports = _empty(ports, 4 * nports, "int64", dev)
+        hdr = _empty(hdr, 8, "int64", dev)
+        need = self._L.pptk_tx_dispatch_scratch_bytes(n, nports)
+        scratch = _empty(scratch, max(need, 256), "uint8", dev)
+        d = Dispatch(n=n, port=_ptr(port), idx=_ptr(idx), flow_port=_ptr(flow_port),
+                     flows=0 if flow_port is None else flow_port.numel(), subject=_ptr(subject),
+                     in_port=_ptr(in_port),
+                     in_port_all=PORT_MAX if in_port_all is None else in_port_all, nports=nports,
+                     miss_code=PORT_DROP if miss_code is None else miss_code, off=_ptr(off),
+                     len=_ptr(lens), stride=stride, fixed_len=fixed_len, list=_ptr(out_list),
+                     out_off=_ptr(out_off), out_len=_ptr(out_len), cap=cap, ports=_ptr(ports),
+                     hdr=_ptr(hdr))
+        _check(self._L.pptk_tx_dispatch_device(self._ctx, ctypes.byref(d), _dp(scratch),
+                                               scratch.numel() * scratch.element_size(),
+                                               _stream(stream, dev)), "pptk_tx_dispatch_device")
+        return dict(hdr=hdr, ports=ports, list=out_list, out_off=out_off, out_len=out_len,
+                    scratch=scratch)
+
     # ---- multi-GPU (RCCL) -------------------------------------------------
     def comm_create(self, nranks, rank, uid):
         """Join communicator `uid` (bytes from comm_uid()) as rank/nranks."""
@@ -1211,6 +1274,63 @@ def flow_learn_shape(lib_path=None):
     learning kernels."""
     b, w = ctypes.c_uint32(), ctypes.c_uint32()
     lib(lib_path).pptk_flow_learn_shape(ctypes.byref(b), ctypes.byref(w))
+    return b.value, w.value
+
+
+def tx_dispatch_host(nports, port=None, idx=None, flow_port=None, miss_code=None, subject=None,
+                     in_port=None, in_port_all=None, off=None, lens=None, stride=0, fixed_len=0,
+                     cap=None, lib_path=None):
+    """pptk_tx_dispatch_host, the CPU statement of tx_dispatch_device, over
+    NumPy arrays: port (uint8) or idx (uint32) with flow_port (uint8) and
+    miss_code (default records.PORT_DROP); subject, in_port (uint8), off
+    (uint64) and lens (uint16) are arrays or None; cap defaults to n.  Returns
+    (hdr, ports, list, out_off, out_len): hdr one records.DISPATCH_HDR_DTYPE
+    entry, ports nports records.DISPATCH_PORT_DTYPE entries, the three arrays
+    cut to hdr.written entries (uint32, uint64, uint16)."""
+    from .records import DISPATCH_HDR_DTYPE, DISPATCH_PORT_DTYPE, PORT_DROP, PORT_MAX
+
+    def arr(x, dtype):
+        return None if x is None else np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+
+    port, idx, flow_port = arr(port, np.uint8), arr(idx, np.uint32), arr(flow_port, np.uint8)
+    subject, in_port = arr(subject, np.uint8), arr(in_port, np.uint8)
+    off, lens = arr(off, np.uint64), arr(lens, np.uint16)
+    if (port is None) == (idx is None):
+        raise ValueError("tx_dispatch_host: exactly one of port / idx")
+    n = len(port if port is not None else idx)
+    if any(x is not None and len(x) != n for x in (subject, in_port, off, lens)):
+        raise ValueError("tx_dispatch_host: subject, in_port, off and lens have n entries")
+    cap = n if cap is None else cap
+    out = (np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint64),
+           np.zeros(max(cap, 1), np.uint16))
+    ports, hdr = np.zeros(max(nports, 1), DISPATCH_PORT_DTYPE), np.zeros(1, DISPATCH_HDR_DTYPE)
+
+    def p(x):
+        return None if x is None else x.ctypes.data
+
+    d = Dispatch(n=n, port=p(port), idx=p(idx), flow_port=p(flow_port),
+                 flows=0 if flow_port is None else len(flow_port), subject=p(subject),
+                 in_port=p(in_port), in_port_all=PORT_MAX if in_port_all is None else in_port_all,
+                 nports=nports, miss_code=PORT_DROP if miss_code is None else miss_code,
+                 off=p(off), len=p(lens), stride=stride, fixed_len=fixed_len,
+                 list=p(out[0]) if cap else None, out_off=p(out[1]), out_len=p(out[2]), cap=cap,
+                 ports=p(ports), hdr=p(hdr))
+    _check(lib(lib_path).pptk_tx_dispatch_host(ctypes.byref(d)), "pptk_tx_dispatch_host")
+    w = int(hdr["written"][0])
+    return hdr[0], ports[:nports], out[0][:w], out[1][:w], out[2][:w]
+
+
+def tx_dispatch_scratch_bytes(n, nports, lib_path=None):
+    """pptk_tx_dispatch_scratch_bytes: the device scratch a dispatch of n
+    frames to nports ports needs (0 for n = 0)."""
+    return lib(lib_path).pptk_tx_dispatch_scratch_bytes(n, nports)
+
+
+def tx_dispatch_shape(lib_path=None):
+    """pptk_tx_dispatch_shape: (block_frames, scan_width) of the library's
+    dispatch kernels."""
+    b, w = ctypes.c_uint32(), ctypes.c_uint32()
+    lib(lib_path).pptk_tx_dispatch_shape(ctypes.byref(b), ctypes.byref(w))
     return b.value, w.value
 
 
