@@ -47,6 +47,7 @@
 // and any interleaving.
 #include <errno.h>
 
+#include "block_scan.h"
 #include "copy16.h"
 #include "rx_internal.h"
 
@@ -108,34 +109,6 @@ struct ReassArgs {
   Slot *slots;
   uint32_t nslots;       // a power of two >= 2 * maxc
 };
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if ((int)lane >= d) x += y;
-  }
-  return x;
-}
-
-// exclusive prefix of v over the workgroup's NW waves and the workgroup's total
-template <int NW>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *lds, uint32_t *total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t incl = wave_incl_scan(v, lane);
-  if (lane == 63) lds[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    const uint32_t t = lds[w];
-    if ((uint32_t)w < wave) base += t;
-    tot += t;
-  }
-  __syncthreads();   // lds is free for the next round
-  *total = tot;
-  return base + incl - v;
-}
 
 __device__ __forceinline__ uint32_t considered_of(const ReassArgs &a) {
   const uint64_t c = a.hdr->considered;
@@ -209,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void reass_classify_kernel(ReassArgs a) {
     a.dgram[i] = kNone;
   }
   uint32_t total;
-  (void)block_excl_scan<kBlock / 64>(st == PPTK_REASS_FST_FRAG, lds, &total);
+  (void)block_excl_scan<kBlock / 64, uint32_t>(st == PPTK_REASS_FST_FRAG, lds, &total);
   if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
 }
 
@@ -222,27 +195,10 @@ __global__ __launch_bounds__(kScan) void reass_scan_kernel(uint32_t *cnt_a, uint
                                                           uint64_t *total_a, uint64_t *min_a,
                                                           uint64_t *total_b) {
   __shared__ uint32_t lds[kScan / 64];
-  uint32_t nb = nb_arg;
-  if (items) {
-    const uint64_t q = (*items + per - 1) / per;
-    if (q < nb) nb = (uint32_t)q;
-  }
-  uint64_t run_a = 0, run_b = 0;
-  for (uint32_t base = 0; base < nb; base += kScan) {
-    const uint32_t k = base + threadIdx.x;
-    uint32_t total;
-    const uint32_t va = k < nb ? cnt_a[k] : 0u;
-    const uint32_t ea = block_excl_scan<kScan / 64>(va, lds, &total);
-    // every sum is at most 2^24
-    if (k < nb) cnt_a[k] = (uint32_t)run_a + ea;
-    run_a += total;
-    if (cnt_b) {
-      const uint32_t vb = k < nb ? cnt_b[k] : 0u;
-      const uint32_t eb = block_excl_scan<kScan / 64>(vb, lds, &total);
-      if (k < nb) cnt_b[k] = (uint32_t)run_b + eb;
-      run_b += total;
-    }
-  }
+  const uint32_t nb = scan_extent(nb_arg, items, per);
+  // every sum is at most 2^24
+  const uint64_t run_a = scan_counts<kScan, uint32_t>(cnt_a, nb, true, lds);
+  const uint64_t run_b = cnt_b ? scan_counts<kScan, uint32_t>(cnt_b, nb, true, lds) : 0;
   if (threadIdx.x == 0) {
     *total_a = run_a;
     *min_a = run_a < limit ? run_a : limit;
@@ -256,7 +212,7 @@ __global__ __launch_bounds__(kBlock) void reass_compact_kernel(ReassArgs a) {
   const bool is = i < a.n && a.fstatus[i] == PPTK_REASS_FST_FRAG;
   uint32_t total;
   // blk + the block's count <= candidates <= 2^24
-  const uint32_t rank = a.blk[blockIdx.x] + block_excl_scan<kBlock / 64>(is, lds, &total);
+  const uint32_t rank = a.blk[blockIdx.x] + block_excl_scan<kBlock / 64, uint32_t>(is, lds, &total);
   if (!is) return;
   if (rank >= a.maxc) {
     a.fstatus[i] = PPTK_REASS_FST_FRAG | PPTK_REASS_FST_SKIPPED;

@@ -37,6 +37,8 @@
 // any grid and any interleaving.
 #include <errno.h>
 
+#include "block_scan.h"
+#include "copy16.h"
 #include "rx_internal.h"
 
 namespace pptk {
@@ -50,8 +52,6 @@ constexpr uint64_t kEmptyTag = ~0ull;
 constexpr uint32_t kNotLeader = 0xffffffffu;
 constexpr uint32_t kAlone = 0xfffffffeu;    // a leader outside the set: count 1
 constexpr uint64_t kMaxCand = 1ull << 30;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct Slot {
   uint64_t tag;
@@ -78,34 +78,6 @@ struct LearnArgs {
   uint64_t cap;
   pptk_flow_learn_hdr *hdr;
 };
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if ((int)lane >= d) x += y;
-  }
-  return x;
-}
-
-// exclusive prefix of v over the workgroup's NW waves and the workgroup's total
-template <int NW>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *lds, uint32_t *total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t incl = wave_incl_scan(v, lane);
-  if (lane == 63) lds[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    const uint32_t t = lds[w];
-    if ((uint32_t)w < wave) base += t;
-    tot += t;
-  }
-  __syncthreads();   // lds is free for the next round
-  *total = tot;
-  return base + incl - v;
-}
 
 __device__ __forceinline__ uint32_t cand_bits(uint32_t w) {
   uint32_t m = 0;
@@ -142,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void learn_count_kernel(LearnArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
   const uint64_t j0 = (uint64_t)blockIdx.x * kFrames + 16u * threadIdx.x;
   uint32_t total;
-  (void)block_excl_scan<kBlock / 64>(__popc(lane_candidates(a, j0)), lds, &total);
+  (void)block_excl_scan<kBlock / 64, uint32_t>(__popc(lane_candidates(a, j0)), lds, &total);
   if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
 }
 
@@ -153,21 +125,9 @@ __global__ __launch_bounds__(kScan) void learn_scan_kernel(uint32_t *cnt, uint32
                                                           uint64_t limit, uint64_t *out_total,
                                                           uint64_t *out_min) {
   __shared__ uint32_t lds[kScan / 64];
-  uint32_t nb = nb_arg;
-  if (items) {
-    const uint64_t q = (*items + per - 1) / per;
-    if (q < nb) nb = (uint32_t)q;
-  }
-  uint64_t running = 0;
-  for (uint32_t base = 0; base < nb; base += kScan) {
-    const uint32_t k = base + threadIdx.x;
-    const uint32_t v = k < nb ? cnt[k] : 0u;
-    uint32_t total;
-    const uint32_t ex = block_excl_scan<kScan / 64>(v, lds, &total);
-    // the sum is at most n < 2^32, so every prefix fits the word
-    if (k < nb) cnt[k] = (uint32_t)running + ex;
-    running += total;
-  }
+  // the sum is at most n < 2^32, so every prefix fits the word
+  const uint64_t running =
+      scan_counts<kScan, uint32_t>(cnt, scan_extent(nb_arg, items, per), true, lds);
   if (threadIdx.x == 0) {
     *out_total = running;
     *out_min = running < limit ? running : limit;
@@ -182,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void learn_compact_kernel(LearnArgs a) {
   uint32_t m = lane_candidates(a, j0);
   uint32_t total;
   // base + the block's count <= candidates < 2^32
-  uint32_t rank = base + block_excl_scan<kBlock / 64>(__popc(m), lds, &total);
+  uint32_t rank = base + block_excl_scan<kBlock / 64, uint32_t>(__popc(m), lds, &total);
   while (m && rank < a.maxc) {   // at most 16 rounds: a bit leaves m in each
     const uint32_t k = __builtin_ctz(m);
     m &= m - 1;
@@ -278,7 +238,7 @@ __global__ __launch_bounds__(kBlock) void learn_resolve_kernel(LearnArgs a) {
     a.lead[r] = code;
   }
   uint32_t total;
-  (void)block_excl_scan<kBlock / 64>(code != kNotLeader, lds, &total);
+  (void)block_excl_scan<kBlock / 64, uint32_t>(code != kNotLeader, lds, &total);
   if (threadIdx.x == 0) a.lcnt[blockIdx.x] = total;
 }
 
@@ -289,8 +249,8 @@ __global__ __launch_bounds__(kBlock) void learn_emit_kernel(LearnArgs a) {
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t code = r < cons ? a.lead[r] : kNotLeader;
   uint32_t total;
-  const uint64_t rank =
-      (uint64_t)a.lcnt[blockIdx.x] + block_excl_scan<kBlock / 64>(code != kNotLeader, lds, &total);
+  const uint64_t rank = (uint64_t)a.lcnt[blockIdx.x] +
+                        block_excl_scan<kBlock / 64, uint32_t>(code != kNotLeader, lds, &total);
   if (code == kNotLeader || rank >= a.cap) return;
   const uint32_t i = a.cand[r];
   const u32x4 *src = (const u32x4 *)(a.recs + i);

@@ -32,6 +32,8 @@
 // Only the byte arrays and idx are staged; off and len are read per lane (8
 // and 2 bytes, consecutive frames in consecutive lanes) where a live frame
 // needs them.
+#include "block_scan.h"
+#include "copy16.h"
 #include "dispatch_check.h"
 #include "rx_internal.h"
 
@@ -49,8 +51,6 @@ constexpr uint32_t kStage = kChunks * 16;
 constexpr uint32_t kNoPort = 64;                // an ingress port at or above nports
 constexpr uint32_t kBadCode = 0xfdu;            // never a port, FLOOD or DROP
 enum Kind : uint32_t { kUni = 0, kFlood = 1, kDrop = 2, kBad = 3, kNone = 4 };
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // the count table's columns, for nports = np
 struct Cols {
@@ -330,15 +330,6 @@ __global__ __launch_bounds__(kBlock) void dispatch_count_kernel(DispArgs a) {
   }
 }
 
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t x, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d);
-    if ((int)lane >= d) x += y;
-  }
-  return x;
-}
-
 // Workgroup c: column c's nblk counts -> their total in tot[c] and, for the
 // first `prefixed` columns, their exclusive prefixes in place.  A prefixed
 // column sums frames of one kind, at most n < 2^32, so its prefixes fit the
@@ -347,26 +338,8 @@ __global__ __launch_bounds__(kScan) void dispatch_scan_kernel(uint32_t *cnt, uin
                                                              uint32_t prefixed, uint64_t *tot) {
   __shared__ uint64_t lds[kScan / 64];
   uint32_t *colp = cnt + (size_t)blockIdx.x * nblk;
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t running = 0;
-  for (uint32_t base = 0; base < nblk; base += kScan) {
-    const uint32_t k = base + threadIdx.x;
-    const uint32_t v = k < nblk ? colp[k] : 0u;
-    const uint64_t incl = wave_incl_scan(v, lane);
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kScan / 64; ++w) {
-      const uint64_t x = lds[w];
-      if ((uint32_t)w < wave) before += x;
-      total += x;
-    }
-    __syncthreads();   // lds is free for the next round
-    if (k < nblk && blockIdx.x < prefixed) colp[k] = (uint32_t)(running + before + incl - v);
-    running += total;
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = running;
+  const uint64_t total = scan_counts<kScan, uint64_t>(colp, nblk, blockIdx.x < prefixed, lds);
+  if (threadIdx.x == 0) tot[blockIdx.x] = total;
 }
 
 // one wave: lane p < nports writes ports[p], lane 0 the header

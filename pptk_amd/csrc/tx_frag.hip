@@ -16,6 +16,7 @@
 // workgroup.
 #include <errno.h>
 
+#include "block_scan.h"
 #include "frame_view.h"
 #include "rx_internal.h"
 
@@ -68,27 +69,6 @@ ScratchLayout scratch_layout(uint64_t n) {
   l.st = l.first + up16(n * 4);
   l.total = l.st + up16(n);
   return l;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t lo = __shfl_up((uint32_t)v, d, 64);
-    const uint32_t hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-    if (lane >= d) v += (uint64_t)lo | ((uint64_t)hi << 32);
-  }
-  return v;
 }
 
 // ---- plan ------------------------------------------------------------------
@@ -149,17 +129,9 @@ __global__ __launch_bounds__(kTile) void frag_plan_kernel(FragArgs a) {
     a.s_st[i] = (uint8_t)st;
   }
   // exclusive prefix inside the tile (at most 256 * 8190 slots: 32 bits)
-  const uint32_t inc = wave_incl_scan(cnt);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t wbase = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kTile / 64; ++w) {
-    if (w < wave) wbase += wsum[w];
-    total += wsum[w];
-  }
-  if (i < a.n) a.s_first[i] = wbase + inc - cnt;
+  uint32_t total;
+  const uint32_t before = block_excl_scan<kTile / 64, uint32_t>(cnt, wsum, &total);
+  if (i < a.n) a.s_first[i] = before;
   if (threadIdx.x == 0) a.s_tile[blockIdx.x] = total;
 }
 
@@ -170,16 +142,10 @@ __global__ __launch_bounds__(kScanThreads) void frag_scan_kernel(FragArgs a, uin
   const uint32_t lo = min(threadIdx.x * per, ntiles), hi = min(lo + per, ntiles);
   uint64_t s = 0;
   for (uint32_t t = lo; t < hi; ++t) s += a.s_tile[t];
-  const uint64_t inc = wave_incl_scan64(s);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint64_t run = inc - s, total = 0;
-#pragma unroll
-  for (int w = 0; w < kScanThreads / 64; ++w) {
-    if (w < wave) run += wsum[w];
-    total += wsum[w];
-  }
+  // each thread sums a contiguous range and one scan runs over the threads'
+  // sums, 64-bit: not the rounds of scan_counts
+  uint64_t total;
+  uint64_t run = block_excl_scan<kScanThreads / 64, uint64_t>(s, wsum, &total);
   for (uint32_t t = lo; t < hi; ++t) {
     const uint64_t v = a.s_tile[t];
     a.s_tile[t] = run;
