@@ -49,6 +49,13 @@ __device__ __forceinline__ uint32_t scan_extent(uint32_t nb, const uint64_t *ite
   return nb;
 }
 
+// a count an earlier pass left in device memory, clamped by the bound the
+// arrays were sized for
+__device__ __forceinline__ uint32_t clamped_count(const uint64_t *count, uint32_t maxc) {
+  const uint64_t c = *count;
+  return c < maxc ? (uint32_t)c : maxc;
+}
+
 // One workgroup of NT threads: the sum of cnt[0 .. nb), and where asked their
 // exclusive prefixes in place, NT counts per round.  T holds the sums of one
 // round; the prefixes are stored as 32-bit words, so the caller bounds them.

@@ -37,6 +37,33 @@ __device__ __forceinline__ uint32_t ld_le32(uintptr_t A) {
   return __builtin_amdgcn_alignbyte(hi, lo, r);
 }
 
+// The outer IPv4 subject test of the ops that take whole frames (tx_frag.hip
+// plan, tx_tunnel.hip decap; host/outer_ipv4.h is its CPU statement): the
+// IPv4 branch of the receive transform's parse (frame_view.h parse_frame) --
+// one optional 802.1Q tag, ethertype 0x0800, version 4, 20 <= ihl <= tl,
+// l2 + tl <= len.  A frame shorter than 14 bytes is not read at all; every
+// other read lies inside the frame.
+struct OuterIpv4 {
+  uint32_t l2, ihl, tl;
+  uint32_t w0, w1, w2;   // the header's first three words, little-endian
+};
+
+__device__ __forceinline__ bool outer_ipv4(uintptr_t F, uint32_t len, OuterIpv4 *o) {
+  if (len < 14 || len > 65535) return false;
+  uint32_t et = (ld_u8(F + 12) << 8) | ld_u8(F + 13), l2 = 14;
+  if (et == 0x8100 && len >= 18) {
+    et = (ld_u8(F + 16) << 8) | ld_u8(F + 17);
+    l2 = 18;
+  }
+  if (et != 0x0800 || len < l2 + 20) return false;
+  const uintptr_t ip = F + l2;
+  const uint32_t w0 = ld_le32(ip), w1 = ld_le32(ip + 4), w2 = ld_le32(ip + 8);
+  const uint32_t b0 = w0 & 0xffu, ihl = (b0 & 15u) * 4u;
+  const uint32_t tl = bswap16(w0 >> 16);
+  *o = {l2, ihl, tl, w0, w1, w2};
+  return (b0 >> 4) == 4 && ihl >= 20 && tl >= ihl && l2 + tl <= len;
+}
+
 // 16 bytes from any byte address A, of which only those below `lim` (> A)
 // are meaningful: the aligned chunk holding A and the aligned chunk holding
 // the last needed byte (the same or the next one), funnelled to A's

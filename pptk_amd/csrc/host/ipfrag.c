@@ -12,6 +12,7 @@
 
 #include "ipcksum.h"
 #include "iphdr.h"
+#include "outer_ipv4.h"
 #include "pptk_rx.h"
 
 int pptk_ip_fragment_host(const void *frame, uint32_t len, uint32_t mtu, uint8_t *out,
@@ -20,32 +21,16 @@ int pptk_ip_fragment_host(const void *frame, uint32_t len, uint32_t mtu, uint8_t
 {
   const unsigned char *f = (const unsigned char *)frame;
   const void *ip;
-  uint32_t l2 = ETHER_HDR_LEN, ihl, tl, datamax, per, count, j;
-  uint16_t et;
+  uint32_t l2, ihl, tl, datamax, per, count, j;
   uint8_t st;
 
   if ((!frame && len) || !out || !out_len || !status || mtu < 68 || mtu > 65535 ||
       out_stride % 16 != 0 || out_stride < ((18u + mtu + 15u) & ~15u))
     return -EINVAL;
   *status = 0;
-  /* the receive transform's parse: one optional 802.1Q tag, IPv4, version,
-   * header and total length consistent with the frame */
-  if (len < ETHER_HDR_LEN || len > 65535)
-    return 0;
-  et = ether_type(f);
-  if (et == 0x8100) {
-    if (len < 18)
-      return 0;
-    et = hdr_get16n(f + 16);
-    l2 = 18;
-  }
-  if (et != ETHER_TYPE_IP || len < l2 + IP_HDR_MINLEN)
+  if (!pptk_outer_ipv4(f, len, &l2, &ihl, &tl))
     return 0;
   ip = f + l2;
-  ihl = ip_hdr_len(ip);
-  tl = ip_total_len(ip);
-  if (ip_version(ip) != 4 || ihl < IP_HDR_MINLEN || tl < ihl || l2 + tl > len)
-    return 0;
 
   st = PPTK_FRAG_ST_IPV4;
   if (tl <= mtu) {

@@ -10,6 +10,7 @@
 
 #include "ipcksum.h"
 #include "iphdr.h"
+#include "outer_ipv4.h"
 #include "pptk_rx.h"
 
 #define GRE_HDR_LEN 4u
@@ -76,30 +77,15 @@ uint32_t pptk_tunnel_decap_host(const void *frame, uint32_t len, uint32_t *in_of
 {
   const unsigned char *f = (const unsigned char *)frame;
   const unsigned char *ip, *gre;
-  uint32_t l2 = ETHER_HDR_LEN, ihl, tl, st;
-  uint16_t et;
+  uint32_t l2, ihl, tl, st;
 
   if (in_off)
     *in_off = 0;
   if (in_len)
     *in_len = 0;
-  /* the outer subject test: pptk_ip_fragment_host's */
-  if (!f || len < ETHER_HDR_LEN || len > 65535)
-    return 0;
-  et = ether_type(f);
-  if (et == 0x8100) {
-    if (len < 18)
-      return 0;
-    et = hdr_get16n(f + 16);
-    l2 = 18;
-  }
-  if (et != ETHER_TYPE_IP || len < l2 + IP_HDR_MINLEN)
+  if (!f || !pptk_outer_ipv4(f, len, &l2, &ihl, &tl))
     return 0;
   ip = f + l2;
-  ihl = ip_hdr_len(ip);
-  tl = ip_total_len(ip);
-  if (ip_version(ip) != 4 || ihl < IP_HDR_MINLEN || tl < ihl || l2 + tl > len)
-    return 0;
   st = PPTK_DECAP_ST_IPV4;
   if (ip_proto(ip) != IP_PROTO_GRE)
     return st;

@@ -50,6 +50,7 @@
 #include "block_scan.h"
 #include "copy16.h"
 #include "rx_internal.h"
+#include "scratch_carve.h"
 
 namespace pptk {
 namespace {
@@ -74,12 +75,7 @@ struct Slot {
 static_assert(sizeof(Slot) == 32, "a slot is 32 bytes");
 
 struct ReassArgs {
-  const uint8_t *frames;
-  const uint64_t *off;   // nullable -> fixed stride
-  const uint16_t *len;   // nullable -> fixed_len
-  uint64_t stride;
-  uint64_t n;
-  uint32_t fixed_len;
+  FrameBatch fb;
   uint32_t maxc;         // min(max_candidates, n)
   const u32x4 *recs;     // 4 chunks per record
   const u32x4 *frag;
@@ -110,20 +106,6 @@ struct ReassArgs {
   uint32_t nslots;       // a power of two >= 2 * maxc
 };
 
-__device__ __forceinline__ uint32_t considered_of(const ReassArgs &a) {
-  const uint64_t c = a.hdr->considered;
-  return c < a.maxc ? (uint32_t)c : a.maxc;
-}
-
-__device__ __forceinline__ uint32_t dgrams_of(const ReassArgs &a) {
-  const uint64_t c = a.hdr->dgrams;
-  return c < a.maxc ? (uint32_t)c : a.maxc;
-}
-
-__device__ __forceinline__ uintptr_t frame_addr(const ReassArgs &a, uint64_t i) {
-  return (uintptr_t)a.frames + (a.off ? a.off[i] : i * a.stride);
-}
-
 __global__ __launch_bounds__(kBlock) void reass_clear_kernel(Slot *slots, uint32_t count) {
   const uint32_t stride = gridDim.x * kBlock;
   for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < count; k += stride) {
@@ -150,13 +132,13 @@ __device__ __forceinline__ Parsed parse_one(const ReassArgs &a, uint64_t i, bool
   const u32x4 fr = a.frag[i];
   const uint32_t l3 = c3.y & 0xffu, fo = fr.y & 0xffffu, dl = fr.y >> 16;
   const uint32_t mf = (fr.w >> 8) & PPTK_RX_FRAG_MF ? 1u : 0u;
-  const uint32_t len = a.len ? a.len[i] : a.fixed_len;
+  const uint32_t len = a.fb.len_at(i);
   uint32_t st = PPTK_REASS_FST_FRAG, ihl = 0;
   if (c2.w & 0xffffu) st |= PPTK_REASS_FST_BADCKSUM;
   if ((l3 != 14 && l3 != 18) || len <= l3) {
     st |= PPTK_REASS_FST_BADFRAG;
   } else {
-    ihl = (ld_u8(frame_addr(a, i) + l3) & 15u) * 4u;
+    ihl = (ld_u8(a.fb.addr(i) + l3) & 15u) * 4u;
     if (ihl < 20 || dl == 0 || fo + dl > 65535 || (mf && (dl & 7u)) || l3 + ihl + dl > len)
       st |= PPTK_REASS_FST_BADFRAG;
   }
@@ -176,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void reass_classify_kernel(ReassArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   uint32_t st = 0;
-  if (i < a.n) {
+  if (i < a.fb.n) {
     st = parse_one(a, i, false).st;
     a.fstatus[i] = (uint8_t)st;
     a.dgram[i] = kNone;
@@ -209,7 +191,7 @@ __global__ __launch_bounds__(kScan) void reass_scan_kernel(uint32_t *cnt_a, uint
 __global__ __launch_bounds__(kBlock) void reass_compact_kernel(ReassArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  const bool is = i < a.n && a.fstatus[i] == PPTK_REASS_FST_FRAG;
+  const bool is = i < a.fb.n && a.fstatus[i] == PPTK_REASS_FST_FRAG;
   uint32_t total;
   // blk + the block's count <= candidates <= 2^24
   const uint32_t rank = a.blk[blockIdx.x] + block_excl_scan<kBlock / 64, uint32_t>(is, lds, &total);
@@ -226,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void reass_compact_kernel(ReassArgs a) {
 
 __global__ __launch_bounds__(kBlock) void reass_insert_kernel(ReassArgs a) {
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
-  if (r >= considered_of(a)) return;
+  if (r >= clamped_count(&a.hdr->considered, a.maxc)) return;
   const u32x4 me = a.key[r];
   const uint32_t mask = a.nslots - 1;
   uint32_t h = me.x * 0x9e3779b1u ^ me.y * 0x85ebca6bu ^ me.z * 0xc2b2ae35u;
@@ -275,7 +257,7 @@ __device__ __forceinline__ void leader_of(const ReassArgs &a, uint32_t r, uint32
 
 __global__ __launch_bounds__(kBlock) void reass_resolve_kernel(ReassArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
-  const uint32_t cons = considered_of(a);
+  const uint32_t cons = clamped_count(&a.hdr->considered, a.maxc);
   if (blockIdx.x * kBlock >= cons) return;   // the whole workgroup
   uint32_t is_lead, run, ta, tb;
   leader_of(a, blockIdx.x * kBlock + threadIdx.x, cons, &is_lead, &run);
@@ -286,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void reass_resolve_kernel(ReassArgs a) {
 
 __global__ __launch_bounds__(kBlock) void reass_assign_kernel(ReassArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
-  const uint32_t cons = considered_of(a);
+  const uint32_t cons = clamped_count(&a.hdr->considered, a.maxc);
   if (blockIdx.x * kBlock >= cons) return;   // the whole workgroup
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   uint32_t is_lead, run, ta, tb;
@@ -302,7 +284,7 @@ __global__ __launch_bounds__(kBlock) void reass_assign_kernel(ReassArgs a) {
 
 __global__ __launch_bounds__(kBlock) void reass_append_kernel(ReassArgs a) {
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
-  if (r >= considered_of(a)) return;
+  if (r >= clamped_count(&a.hdr->considered, a.maxc)) return;
   const uint32_t s = a.cslot[r];
   if (s >= a.nslots) return;
   Slot *sl = a.slots + s;
@@ -316,7 +298,7 @@ __global__ __launch_bounds__(kBlock) void reass_decide_kernel(ReassArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (blockIdx.x * kBlock + threadIdx.x) >> 6;
   const uint32_t nwaves = gridDim.x * (kBlock / 64);
-  const uint32_t ndg = dgrams_of(a);
+  const uint32_t ndg = clamped_count(&a.hdr->dgrams, a.maxc);
   for (uint32_t k = wave; k < ndg; k += nwaves) {
     const uint32_t r0 = a.lead[k];
     const Slot sl = a.slots[a.cslot[r0]];
@@ -380,7 +362,7 @@ __device__ __forceinline__ void dg_kind(const ReassArgs &a, uint32_t k, uint32_t
 
 __global__ __launch_bounds__(kBlock) void reass_count_kernel(ReassArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
-  const uint32_t ndg = dgrams_of(a);
+  const uint32_t ndg = clamped_count(&a.hdr->dgrams, a.maxc);
   if (blockIdx.x * kBlock >= ndg) return;   // the whole workgroup
   uint32_t st, elig, comp, ta, tb;
   dg_kind(a, blockIdx.x * kBlock + threadIdx.x, ndg, &st, &elig, &comp);
@@ -391,7 +373,7 @@ __global__ __launch_bounds__(kBlock) void reass_count_kernel(ReassArgs a) {
 
 __global__ __launch_bounds__(kBlock) void reass_finish_kernel(ReassArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
-  const uint32_t ndg = dgrams_of(a);
+  const uint32_t ndg = clamped_count(&a.hdr->dgrams, a.maxc);
   if (blockIdx.x * kBlock >= ndg) return;   // the whole workgroup
   const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
   uint32_t st, elig, comp, ta;
@@ -416,7 +398,7 @@ __global__ __launch_bounds__(kBlock) void reass_finish_kernel(ReassArgs a) {
 
 __global__ __launch_bounds__(kBlock) void reass_frames_kernel(ReassArgs a) {
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
-  if (r >= considered_of(a)) return;
+  if (r >= clamped_count(&a.hdr->considered, a.maxc)) return;
   const uint32_t s = a.cslot[r];
   if (s >= a.nslots) return;
   const uint32_t k = a.slots[s].dg, i = a.cand[r];
@@ -440,7 +422,7 @@ __device__ __forceinline__ void emit_dgram(const ReassArgs &a, uint32_t k, uint3
   const uint32_t cnt = sl.count < kMaxFrags ? sl.count : kMaxFrags;
   const uint32_t mt0 = a.meta[r0], l2 = mt0 & 0xffu, ihl = (mt0 >> 8) & 0xffu, H = l2 + ihl;
   const uint32_t flen = a.dlen[k], total = flen - H;
-  const uintptr_t F = frame_addr(a, a.cand[r0]);
+  const uintptr_t F = a.fb.addr(a.cand[r0]);
   uint8_t *slot = a.out + (uint64_t)a.dslot[k] * a.out_stride;
 
   // The team's lanes are in one wave, whose LDS accesses keep their order.
@@ -448,7 +430,7 @@ __device__ __forceinline__ void emit_dgram(const ReassArgs &a, uint32_t k, uint3
   for (uint32_t p = t; p < cnt; p += kTeam) {
     const uint32_t m = a.mem[sl.base + p], mt = a.meta[m];
     L->ol[p] = a.key[m].w;
-    L->src[p] = frame_addr(a, a.cand[m]) + (mt & 0xffu) + ((mt >> 8) & 0xffu);
+    L->src[p] = a.fb.addr(a.cand[m]) + (mt & 0xffu) + ((mt >> 8) & 0xffu);
   }
   // the header: the leader's, offset and MF cleared (DF and the reserved bit
   // stay), the new total length, the checksum over the patched bytes
@@ -526,20 +508,14 @@ __global__ __launch_bounds__(kBlock) void reass_emit_kernel(ReassArgs a) {
   const uint32_t t = threadIdx.x & (kTeam - 1);
   const uint32_t team = (blockIdx.x * kBlock + threadIdx.x) / kTeam;
   const uint32_t nteams = gridDim.x * (kBlock / kTeam);
-  const uint32_t ndg = dgrams_of(a);
+  const uint32_t ndg = clamped_count(&a.hdr->dgrams, a.maxc);
   for (uint32_t k = team; k < ndg; k += nteams)
     if (a.dstat[k] & PPTK_REASS_DG_WRITTEN) emit_dgram(a, k, t, L);
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
-size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
-// where the arrays lie in the scratch
+// the derived counts of a call
 struct Layout {
   uint32_t maxc, nslots, nblk, ncblk;
-  size_t blk, cand, key, meta, cslot, mem, cnt_a, cnt_b, lead, dstat, dlen, dslot, junk, slots,
-      total;
 };
 
 bool layout_of(uint64_t n, uint64_t max_candidates, Layout *l) {
@@ -549,29 +525,28 @@ bool layout_of(uint64_t n, uint64_t max_candidates, Layout *l) {
   while (l->nslots < 2ull * l->maxc) l->nslots <<= 1;
   l->nblk = (uint32_t)((n + kBlock - 1) / kBlock);
   l->ncblk = (l->maxc + kBlock - 1) / kBlock;
-  const size_t words = up256((size_t)l->maxc * 4), blocks = up256((size_t)l->ncblk * 4);
-  size_t at = 0;
-  l->blk = at, at += up256((size_t)l->nblk * 4);
-  l->cand = at, at += words;
-  l->key = at, at += up256((size_t)l->maxc * 16);
-  l->meta = at, at += words;
-  l->cslot = at, at += words;
-  l->mem = at, at += words;
-  l->cnt_a = at, at += blocks;
-  l->cnt_b = at, at += blocks;
-  l->lead = at, at += words;
-  l->dstat = at, at += words;
-  l->dlen = at, at += words;
-  l->dslot = at, at += words;
-  l->junk = at, at += 256;
-  l->slots = at, at += up256((size_t)l->nslots * sizeof(Slot));
-  l->total = at;
   return true;
 }
 
-uint32_t grid_of(uint32_t items, uint32_t per) {
-  const uint32_t g = (items + per - 1) / per;
-  return g < kMaxGrid ? g : kMaxGrid;
+// the scratch's arrays, in order: without a base the walk sizes the scratch,
+// with the scratch pointer it binds the arguments
+size_t carve(const Layout &l, void *base, ReassArgs *a) {
+  Carve c(base, 256);
+  a->blk = c.take<uint32_t>(l.nblk);
+  a->cand = c.take<uint32_t>(l.maxc);
+  a->key = c.take<u32x4>(l.maxc);
+  a->meta = c.take<uint32_t>(l.maxc);
+  a->cslot = c.take<uint32_t>(l.maxc);
+  a->mem = c.take<uint32_t>(l.maxc);
+  a->cnt_a = c.take<uint32_t>(l.ncblk);
+  a->cnt_b = c.take<uint32_t>(l.ncblk);
+  a->lead = c.take<uint32_t>(l.maxc);
+  a->dstat = c.take<uint32_t>(l.maxc);
+  a->dlen = c.take<uint32_t>(l.maxc);
+  a->dslot = c.take<uint32_t>(l.maxc);
+  a->junk = c.take<uint64_t>(2);
+  a->slots = c.take<Slot>(l.nslots);
+  return c.total();
 }
 
 }  // namespace
@@ -586,7 +561,8 @@ extern "C" void pptk_ip_reass_shape(uint32_t *max_frags, uint32_t *block_frames)
 
 extern "C" size_t pptk_ip_reass_scratch_bytes(uint64_t n, uint64_t max_candidates) {
   Layout l;
-  return layout_of(n, max_candidates, &l) ? l.total : 0;
+  ReassArgs a;
+  return layout_of(n, max_candidates, &l) ? carve(l, nullptr, &a) : 0;
 }
 
 extern "C" int pptk_ip_reass_device(struct pptk_rx_ctx *c, const uint8_t *d_frames,
@@ -610,11 +586,13 @@ extern "C" int pptk_ip_reass_device(struct pptk_rx_ctx *c, const uint8_t *d_fram
     return -EINVAL;
   if ((out_cap && (!d_out || !d_out_len)) || (report_cap && !d_report)) return -EINVAL;
   Layout l;
+  ReassArgs a;
   if (n) {
-    if (!d_frames || !d_recs || !d_frag || !d_dgram || !d_fstatus ||
-        (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535))
+    if (!frame_batch_ok(d_frames, d_off, d_len, stride, fixed_len, n) || !d_recs || !d_frag ||
+        !d_dgram || !d_fstatus)
       return -EINVAL;
-    if (!layout_of(n, max_candidates, &l) || !d_scratch || scratch_bytes < l.total)
+    if (!layout_of(n, max_candidates, &l) || !d_scratch ||
+        scratch_bytes < carve(l, d_scratch, &a))
       return -EINVAL;
   }
   DeviceScope dg(ctx_device(c));
@@ -622,14 +600,7 @@ extern "C" int pptk_ip_reass_device(struct pptk_rx_ctx *c, const uint8_t *d_fram
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) return hip_rc(hipMemsetAsync(d_hdr, 0, sizeof(*d_hdr), s));
 
-  uint8_t *base = (uint8_t *)d_scratch;
-  ReassArgs a;
-  a.frames = d_frames;
-  a.off = d_off;
-  a.len = d_len;
-  a.stride = stride;
-  a.n = n;
-  a.fixed_len = fixed_len;
+  a.fb = {d_frames, d_off, d_len, stride, n, fixed_len};
   a.maxc = l.maxc;
   a.recs = (const u32x4 *)d_recs;
   a.frag = (const u32x4 *)d_frag;
@@ -642,25 +613,11 @@ extern "C" int pptk_ip_reass_device(struct pptk_rx_ctx *c, const uint8_t *d_fram
   a.dgram = d_dgram;
   a.fstatus = d_fstatus;
   a.hdr = d_hdr;
-  a.blk = (uint32_t *)(base + l.blk);
-  a.cand = (uint32_t *)(base + l.cand);
-  a.key = (u32x4 *)(base + l.key);
-  a.meta = (uint32_t *)(base + l.meta);
-  a.cslot = (uint32_t *)(base + l.cslot);
-  a.mem = (uint32_t *)(base + l.mem);
-  a.cnt_a = (uint32_t *)(base + l.cnt_a);
-  a.cnt_b = (uint32_t *)(base + l.cnt_b);
-  a.lead = (uint32_t *)(base + l.lead);
-  a.dstat = (uint32_t *)(base + l.dstat);
-  a.dlen = (uint32_t *)(base + l.dlen);
-  a.dslot = (uint32_t *)(base + l.dslot);
-  a.junk = (uint64_t *)(base + l.junk);
-  a.slots = (Slot *)(base + l.slots);
   a.nslots = l.nslots;
   const dim3 blk(kBlock), frames(l.nblk), cands(l.ncblk);
   const uint64_t *none = nullptr;
-  hipLaunchKernelGGL(reass_clear_kernel, dim3(grid_of(l.nslots, kBlock)), blk, 0, s, a.slots,
-                     l.nslots);
+  hipLaunchKernelGGL(reass_clear_kernel, dim3(capped_grid(l.nslots, kBlock, kMaxGrid)), blk, 0, s,
+                     a.slots, l.nslots);
   hipLaunchKernelGGL(reass_classify_kernel, frames, blk, 0, s, a);
   hipLaunchKernelGGL(reass_scan_kernel, dim3(1), dim3(kScan), 0, s, a.blk, (uint32_t *)nullptr,
                      l.nblk, none, 1u, (uint64_t)l.maxc, &d_hdr->candidates, &d_hdr->considered,
@@ -675,13 +632,15 @@ extern "C" int pptk_ip_reass_device(struct pptk_rx_ctx *c, const uint8_t *d_fram
                      &d_hdr->dgrams, &d_hdr->reported, a.junk);
   hipLaunchKernelGGL(reass_assign_kernel, cands, blk, 0, s, a);
   hipLaunchKernelGGL(reass_append_kernel, cands, blk, 0, s, a);
-  hipLaunchKernelGGL(reass_decide_kernel, dim3(grid_of(l.maxc, kBlock / 64)), blk, 0, s, a);
+  hipLaunchKernelGGL(reass_decide_kernel, dim3(capped_grid(l.maxc, kBlock / 64, kMaxGrid)), blk,
+                     0, s, a);
   hipLaunchKernelGGL(reass_count_kernel, cands, blk, 0, s, a);
   hipLaunchKernelGGL(reass_scan_kernel, dim3(1), dim3(kScan), 0, s, a.cnt_a, a.cnt_b, l.ncblk,
                      (const uint64_t *)&d_hdr->dgrams, (uint32_t)kBlock, out_cap, a.junk + 1,
                      &d_hdr->written, &d_hdr->complete);
   hipLaunchKernelGGL(reass_finish_kernel, cands, blk, 0, s, a);
   hipLaunchKernelGGL(reass_frames_kernel, cands, blk, 0, s, a);
-  hipLaunchKernelGGL(reass_emit_kernel, dim3(grid_of(l.maxc, kBlock / kTeam)), blk, 0, s, a);
+  hipLaunchKernelGGL(reass_emit_kernel, dim3(capped_grid(l.maxc, kBlock / kTeam, kMaxGrid)), blk,
+                     0, s, a);
   return hip_rc(hipGetLastError());
 }

@@ -97,8 +97,6 @@ static void drop_split_streams(pptk_rx_ctx *c) {
   c->split_cus = 0;
 }
 
-static int hip_err(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
 static uint64_t le64(const uint8_t *p) {
   uint64_t v = 0;
   for (int i = 7; i >= 0; --i) v = (v << 8) | p[i];
@@ -115,14 +113,13 @@ static int hdr_op(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_t *d_of
                   uint8_t *d_status, bool op_ok, Launch launch) {
   if (!c || n > 0xffffffffull) return -EINVAL;
   if (n == 0) return 0;
-  if (!d_frames || !op_ok || (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535))
-    return -EINVAL;
+  if (!op_ok || !frame_batch_ok(d_frames, d_off, d_len, stride, fixed_len, n)) return -EINVAL;
   DeviceScope dg(c->device);
   if (!dg.ok) return -EIO;
-  const HdrBatch b = {d_frames, d_frames, d_off, d_len, stride, n, fixed_len, d_status};
+  const HdrBatch b = {{d_frames, d_off, d_len, stride, n, fixed_len}, d_frames, d_status};
   const uint64_t blocks = (n + 255) / 256;
   const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)c->ncu * 8);
-  return hip_err(launch(b, grid));
+  return hip_rc(launch(b, grid));
 }
 
 extern "C" {
@@ -313,10 +310,10 @@ static uint64_t gcd64(uint64_t a, uint64_t b) {
 static int check_batch(const pptk_rx_ctx *c, const pptk_rx_dev_batch *b) {
   if (!c || !b) return -EINVAL;
   if (b->n == 0) return 0;
-  if (!b->d_frames || (!b->d_recs && !b->d_recs32)) return -EINVAL;
+  if (!b->d_recs && !b->d_recs32) return -EINVAL;
   if (b->n > 0xffffffffull) return -EINVAL;  // indices are 32-bit (d_perm)
-  if (!b->d_off && b->stride == 0 && b->n > 1) return -EINVAL;
-  if (!b->d_len && b->fixed_len > 65535) return -EINVAL;
+  if (!frame_batch_ok(b->d_frames, b->d_off, b->d_len, b->stride, b->fixed_len, b->n))
+    return -EINVAL;
   return 0;
 }
 
@@ -391,7 +388,7 @@ static int launch_batch(pptk_rx_ctx *c, const pptk_rx_dev_batch *b, int variant,
   // (the period follows the waves resident at once, not the whole grid)
   a.phase_ticks = phase_ticks_for(
       b, variant, (int)std::min<uint64_t>((uint64_t)grid, resident_blocks(c, variant)));
-  return hip_err(launch_rx(variant, a, grid, (hipStream_t)stream));
+  return hip_rc(launch_rx(variant, a, grid, (hipStream_t)stream));
 }
 
 int pptk_rx_batch_device(struct pptk_rx_ctx *c, const struct pptk_rx_dev_batch *b,
@@ -643,9 +640,9 @@ int pptk_tx_cksum_device(struct pptk_rx_ctx *c, uint8_t *d_frames, const uint64_
     hipError_t e = launch_rx(variant, a, grid_for(c, variant, n), s);
     if (e == hipSuccess) e = launch_tx_apply(side, d_frames, d_off, stride, n, s);
     if (pooled && hipFreeAsync(side, s) != hipSuccess && e == hipSuccess) e = hipErrorUnknown;
-    return hip_err(e);
+    return hip_rc(e);
   }
-  return hip_err(launch_rx(variant, a, grid_for(c, variant, n), s));
+  return hip_rc(launch_rx(variant, a, grid_for(c, variant, n), s));
 }
 
 int pptk_tx_set_side_buffer(struct pptk_rx_ctx *c, void *d_side, uint64_t frames) {
@@ -722,7 +719,7 @@ int pptk_rx_batch_device_mixed(struct pptk_rx_ctx *c, const struct pptk_rx_dev_b
     pptk_rx_dev_batch t = *b;
     t.d_perm = nullptr;
     if ((rc = pptk_rx_batch_device(c, &t, stream)) != 0) return rc;
-    return d_perm ? hip_err(launch_iota(d_perm, b->n, s)) : 0;
+    return d_perm ? hip_rc(launch_iota(d_perm, b->n, s)) : 0;
   }
   uint32_t *perm = d_perm ? d_perm : bin_perm(d_scratch, kBinGrid, b->n);
   // the binning also lays the descriptors out in binned order (scratch), so
@@ -843,7 +840,7 @@ int pptk_rx_stream_destroy(void *stream) {
     if (g_split_owned.count(s)) return -EBUSY;   // its context destroys it
     if (g_split_retired.erase(s)) return 0;      // its context already did
   }
-  return hip_err(hipStreamDestroy(s));
+  return hip_rc(hipStreamDestroy(s));
 }
 
 int pptk_rx_variant_count(void) { return RX_NVARIANTS; }
@@ -883,7 +880,7 @@ static int permit_common(struct pptk_rx_ctx *c, const struct pptk_rx_rec *d_recs
   a.ncu = c->ncu - c->coll_cus;
   a.force_passes =
       c->permit_passes || (env_tune() >= 0 && (env_tune() & PPTK_RX_TUNE_PERMIT_PASSES)) ? 1 : 0;
-  return hip_err(launch_permit(a, d_scratch, (hipStream_t)stream));
+  return hip_rc(launch_permit(a, d_scratch, (hipStream_t)stream));
 }
 
 int pptk_rx_permit_status(struct pptk_rx_ctx *c, const void *d_scratch, void *stream) {
@@ -916,7 +913,7 @@ int pptk_rx_tokens_refill_device(struct pptk_rx_ctx *c, uint32_t *d_tokens, uint
   if (!c || !d_tokens || start > end || end > c->opts.iphash_size) return -EINVAL;
   DeviceScope dg(c->device);
   if (!dg.ok) return -EIO;
-  return hip_err(launch_refill(d_tokens, start, end, add, initial_tokens, (hipStream_t)stream));
+  return hip_rc(launch_refill(d_tokens, start, end, add, initial_tokens, (hipStream_t)stream));
 }
 
 size_t pptk_rx_bin_scratch_bytes(uint64_t n) { return bin_scratch_bytes(n, kBinGrid); }
@@ -927,7 +924,7 @@ int pptk_rx_bin_device(struct pptk_rx_ctx *c, const uint16_t *d_len, uint64_t n,
   if (n > 0xffffffffull) return -EINVAL;
   DeviceScope dg(c->device);
   if (!dg.ok) return -EIO;
-  return hip_err(launch_bin(d_len, n, d_perm, d_scratch, (hipStream_t)stream, kBinGrid,
+  return hip_rc(launch_bin(d_len, n, d_perm, d_scratch, (hipStream_t)stream, kBinGrid,
                             BinDesc{nullptr, 0, nullptr, nullptr}, kBinBounds, false));
 }
 

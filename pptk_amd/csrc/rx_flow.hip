@@ -16,6 +16,7 @@
 //           it going.  No atomics; every store is a plain vector store.
 #include <errno.h>
 
+#include "copy16.h"
 #include "flowtab.h"
 #include "rx_internal.h"
 
@@ -40,8 +41,6 @@ constexpr int kTeam = PPTK_FLOW_TEAM;
 constexpr int kTeam = 1;
 #endif
 static_assert(kTeam == 1 || kTeam == 4, "PPTK_FLOW_TEAM is 1 or 4");
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct FlowArgs {
   const pptk_flow_slot *img;
@@ -146,8 +145,6 @@ __global__ __launch_bounds__(kBlock) void flow_lookup_kernel_4(FlowArgs a) {
   }
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
 }  // namespace
 }  // namespace pptk
 
@@ -233,9 +230,7 @@ extern "C" int pptk_flow_lookup_device(struct pptk_rx_ctx *c, const struct pptk_
   a.n = n;
   a.mask = t->slots - 1;
   a.limit = t->d_probe_limit < t->slots ? t->d_probe_limit : t->slots;
-  const uint64_t per_block = kBlock / kTeam;
-  const uint64_t blocks = (n + per_block - 1) / per_block;
-  const dim3 grid((uint32_t)(blocks < kMaxGrid ? blocks : kMaxGrid));
+  const dim3 grid(capped_grid(n, kBlock / kTeam, kMaxGrid));
   if (kTeam == 4)
     hipLaunchKernelGGL(flow_lookup_kernel_4, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
   else

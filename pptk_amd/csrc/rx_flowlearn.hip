@@ -40,6 +40,7 @@
 #include "block_scan.h"
 #include "copy16.h"
 #include "rx_internal.h"
+#include "scratch_carve.h"
 
 namespace pptk {
 namespace {
@@ -150,14 +151,9 @@ __global__ __launch_bounds__(kBlock) void learn_compact_kernel(LearnArgs a) {
   }
 }
 
-__device__ __forceinline__ uint32_t considered_of(const LearnArgs &a) {
-  const uint64_t c = a.hdr->considered;
-  return c < a.maxc ? (uint32_t)c : a.maxc;
-}
-
 __global__ __launch_bounds__(kBlock) void learn_insert_kernel(LearnArgs a) {
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
-  if (r >= considered_of(a)) return;
+  if (r >= clamped_count(&a.hdr->considered, a.maxc)) return;
   const uint64_t h = a.recs[a.cand[r]].flow_hash;
   const uint32_t mask = a.nslots - 1;
   uint32_t s = (uint32_t)h & mask;
@@ -188,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void learn_insert_kernel(LearnArgs a) {
 
 __global__ __launch_bounds__(kBlock) void learn_resolve_kernel(LearnArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
-  const uint32_t cons = considered_of(a);
+  const uint32_t cons = clamped_count(&a.hdr->considered, a.maxc);
   if (blockIdx.x * kBlock >= cons) return;   // the whole workgroup
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   uint32_t code = kNotLeader;
@@ -244,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void learn_resolve_kernel(LearnArgs a) {
 
 __global__ __launch_bounds__(kBlock) void learn_emit_kernel(LearnArgs a) {
   __shared__ uint32_t lds[kBlock / 64];
-  const uint32_t cons = considered_of(a);
+  const uint32_t cons = clamped_count(&a.hdr->considered, a.maxc);
   if (blockIdx.x * kBlock >= cons) return;   // the whole workgroup
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t code = r < cons ? a.lead[r] : kNotLeader;
@@ -261,14 +257,9 @@ __global__ __launch_bounds__(kBlock) void learn_emit_kernel(LearnArgs a) {
   if (a.packets) a.packets[rank] = code == kAlone ? 1u : a.slots[code].count;
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
-size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
-// where the arrays lie in the scratch
+// the derived counts of a call
 struct Layout {
   uint32_t maxc, nslots, nblk, nlblk;
-  size_t blk, cand, lead, lcnt, slots, total;
 };
 
 bool layout_of(uint64_t n, uint64_t max_candidates, Layout *l) {
@@ -279,14 +270,19 @@ bool layout_of(uint64_t n, uint64_t max_candidates, Layout *l) {
   while (l->nslots < 2ull * l->maxc) l->nslots <<= 1;
   l->nblk = (uint32_t)((n + 15 + kFrames - 1) / kFrames);   // whatever the phase of d_status
   l->nlblk = (l->maxc + kBlock - 1) / kBlock;
-  size_t at = 0;
-  l->blk = at, at += up256((size_t)l->nblk * 4);
-  l->cand = at, at += up256((size_t)l->maxc * 4);
-  l->lead = at, at += up256((size_t)l->maxc * 4);
-  l->lcnt = at, at += up256((size_t)l->nlblk * 4);
-  l->slots = at, at += up256(((size_t)l->nslots + 1) * sizeof(Slot));
-  l->total = at;
   return true;
+}
+
+// the scratch's arrays, in order: without a base the walk sizes the scratch,
+// with the scratch pointer it binds the arguments
+size_t carve(const Layout &l, void *base, LearnArgs *a) {
+  Carve c(base, 256);
+  a->blk = c.take<uint32_t>(l.nblk);
+  a->cand = c.take<uint32_t>(l.maxc);
+  a->lead = c.take<uint32_t>(l.maxc);
+  a->lcnt = c.take<uint32_t>(l.nlblk);
+  a->slots = c.take<Slot>((size_t)l.nslots + 1);
+  return c.total();
 }
 
 }  // namespace
@@ -301,7 +297,8 @@ extern "C" void pptk_flow_learn_shape(uint32_t *block_frames, uint32_t *scan_wid
 
 extern "C" size_t pptk_flow_learn_scratch_bytes(uint64_t n, uint64_t max_candidates) {
   Layout l;
-  return layout_of(n, max_candidates, &l) ? l.total : 0;
+  LearnArgs a;
+  return layout_of(n, max_candidates, &l) ? carve(l, nullptr, &a) : 0;
 }
 
 extern "C" int pptk_flow_learn_device(struct pptk_rx_ctx *c, const struct pptk_rx_rec *d_recs,
@@ -319,8 +316,11 @@ extern "C" int pptk_flow_learn_device(struct pptk_rx_ctx *c, const struct pptk_r
       ((uintptr_t)d_first & 3u) || ((uintptr_t)d_packets & 3u) || ((uintptr_t)d_scratch & 255u))
     return -EINVAL;
   Layout l;
+  LearnArgs a;
   if (n) {
-    if (!layout_of(n, max_candidates, &l) || !d_scratch || scratch_bytes < l.total) return -EINVAL;
+    if (!layout_of(n, max_candidates, &l) || !d_scratch ||
+        scratch_bytes < carve(l, d_scratch, &a))
+      return -EINVAL;
   }
   DeviceScope dg(ctx_device(c));
   if (!dg.ok) return -EIO;
@@ -329,18 +329,11 @@ extern "C" int pptk_flow_learn_device(struct pptk_rx_ctx *c, const struct pptk_r
     if (!d_hdr) return 0;
     return hip_rc(hipMemsetAsync(d_hdr, 0, sizeof(*d_hdr), s));
   }
-  uint8_t *base = (uint8_t *)d_scratch;
-  LearnArgs a;
   a.status = d_status;
   a.recs = d_recs;
   a.n = n;
   a.phase = (uint32_t)((uintptr_t)d_status & 15u);
   a.maxc = l.maxc;
-  a.blk = (uint32_t *)(base + l.blk);
-  a.cand = (uint32_t *)(base + l.cand);
-  a.lead = (uint32_t *)(base + l.lead);
-  a.lcnt = (uint32_t *)(base + l.lcnt);
-  a.slots = (Slot *)(base + l.slots);
   a.nslots = l.nslots;
   a.new_recs = d_new_recs;
   a.first = d_first;
@@ -348,10 +341,9 @@ extern "C" int pptk_flow_learn_device(struct pptk_rx_ctx *c, const struct pptk_r
   a.cap = cap;
   a.hdr = d_hdr;
   const uint32_t nblk = (uint32_t)((n + a.phase + kFrames - 1) / kFrames);   // <= l.nblk
-  const uint32_t clear_blocks = (l.nslots + 1 + kBlock - 1) / kBlock;
   const dim3 blk(kBlock);
-  hipLaunchKernelGGL(learn_clear_kernel, dim3(clear_blocks < kMaxGrid ? clear_blocks : kMaxGrid),
-                     blk, 0, s, a.slots, l.nslots + 1);
+  hipLaunchKernelGGL(learn_clear_kernel, dim3(capped_grid(l.nslots + 1, kBlock, kMaxGrid)), blk, 0,
+                     s, a.slots, l.nslots + 1);
   hipLaunchKernelGGL(learn_count_kernel, dim3(nblk), blk, 0, s, a);
   hipLaunchKernelGGL(learn_scan_kernel, dim3(1), dim3(kScan), 0, s, a.blk, nblk,
                      (const uint64_t *)nullptr, 1u, (uint64_t)l.maxc, &d_hdr->candidates,

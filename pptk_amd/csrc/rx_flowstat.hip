@@ -31,6 +31,7 @@
 //   make abvariant NAME=flowstat_direct DEFS=-DPPTK_FLOWSTAT_DIRECT=1
 #include <errno.h>
 
+#include "copy16.h"
 #include "rx_internal.h"
 
 namespace pptk {
@@ -53,7 +54,6 @@ constexpr bool kDirect = PPTK_FLOWSTAT_DIRECT != 0;
 constexpr bool kDirect = false;
 #endif
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 struct StatArgs {
@@ -272,8 +272,6 @@ __global__ __launch_bounds__(kBlock) void flow_stats_reset_kernel(ResetArgs a) {
   }
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
 bool stats_ok(const void *stats, uint64_t stats_count) {
   return stats_count != 0 && stats_count <= (1ull << 32) && !((uintptr_t)stats & 31u);
 }
@@ -313,14 +311,12 @@ extern "C" int pptk_flow_account_device(struct pptk_rx_ctx *c, const uint32_t *d
   a.fixed_len = fixed_len;
   a.phase = (uint32_t)((uintptr_t)d_idx >> 2) & 3u;
   if (kDirect) {
-    const uint64_t blocks = (n + kBlock - 1) / kBlock;
-    const dim3 grid((uint32_t)(blocks < kMaxGrid ? blocks : kMaxGrid));
+    const dim3 grid(capped_grid(n, kBlock, kMaxGrid));
     hipLaunchKernelGGL(flow_account_direct_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
   } else {
     // one workgroup per segment: many more workgroups than CUs, so the
     // dispatcher balances segments of uneven cost
-    const uint64_t nseg = (n + a.phase + kSeg - 1) / kSeg;
-    const dim3 grid((uint32_t)(nseg < kMaxGrid ? nseg : kMaxGrid));
+    const dim3 grid(capped_grid(n + a.phase, kSeg, kMaxGrid));
     hipLaunchKernelGGL(flow_account_seg_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
   }
   return hip_rc(hipGetLastError());
@@ -335,8 +331,7 @@ extern "C" int pptk_flow_stats_reset_device(struct pptk_rx_ctx *c, struct pptk_f
   if (!dg.ok) return -EIO;
   if (count == 0) return 0;
   const ResetArgs a = {d_stats, d_values, stats_count, count, now};
-  const uint64_t blocks = (count + kBlock - 1) / kBlock;
-  const dim3 grid((uint32_t)(blocks < kMaxGrid ? blocks : kMaxGrid));
+  const dim3 grid(capped_grid(count, kBlock, kMaxGrid));
   hipLaunchKernelGGL(flow_stats_reset_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
   return hip_rc(hipGetLastError());
 }

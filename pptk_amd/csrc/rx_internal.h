@@ -1,5 +1,6 @@
 // rx_internal.h -- shared between the kernels and the C-ABI shim.
 #pragma once
+#include <errno.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -55,6 +56,40 @@ void host_pipe_destroy(HostPipe *hp);
 inline long env_long(const char *name, long dflt) {
   const char *e = getenv(name);
   return e ? atol(e) : dflt;
+}
+
+// what a C-ABI entry point returns for a HIP call or launch
+inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
+
+// a grid of ceil(items / per) workgroups, at most cap: beyond it the kernel
+// strides over the items
+inline uint32_t capped_grid(uint64_t items, uint64_t per, uint32_t cap) {
+  const uint64_t g = (items + per - 1) / per;
+  return (uint32_t)(g < cap ? g : cap);
+}
+
+// A batch of frames in device memory as every batch op is handed it: frame i
+// lies at off[i], or at i * stride without an offset array, and is len[i]
+// bytes long, or fixed_len without a length array.  The ops' argument structs
+// hold one as their first member (the receive kernels keep RxKArgs).
+struct FrameBatch {
+  const uint8_t *frames;
+  const uint64_t *off;   // nullable -> fixed stride
+  const uint16_t *len;   // nullable -> fixed_len
+  uint64_t stride;
+  uint64_t n;
+  uint32_t fixed_len;
+
+  __device__ __forceinline__ uint64_t base(uint64_t i) const { return off ? off[i] : i * stride; }
+  __device__ __forceinline__ uint32_t len_at(uint64_t i) const { return len ? len[i] : fixed_len; }
+  __device__ __forceinline__ uintptr_t addr(uint64_t i) const {
+    return (uintptr_t)frames + base(i);
+  }
+};
+// whether an entry point's arguments describe a usable batch
+inline bool frame_batch_ok(const uint8_t *frames, const uint64_t *off, const uint16_t *len,
+                           uint64_t stride, uint32_t fixed_len, uint64_t n) {
+  return n == 0 || (frames && (off || stride || n == 1) && (len || fixed_len <= 65535));
 }
 
 // Kernel arguments (by value; a handful of SGPRs).
@@ -165,13 +200,8 @@ hipError_t launch_tx_apply(const uint64_t *txside, uint8_t *frames, const uint64
 // layout -- does not change with them.  All three work on a batch of frames
 // edited in place:
 struct HdrBatch {
-  const uint8_t *frames;
+  FrameBatch fb;
   uint8_t *frames_w;     // the same frames, writable
-  const uint64_t *off;   // nullable -> fixed stride
-  const uint16_t *len;   // nullable -> fixed_len
-  uint64_t stride;
-  uint64_t n;
-  uint32_t fixed_len;
   uint8_t *status;       // nullable: per-frame status byte
 };
 // header rewrite (pptk_tx_rewrite_device, pptk_tx_rewrite_flow_device)

@@ -36,6 +36,7 @@
 #include "copy16.h"
 #include "dispatch_check.h"
 #include "rx_internal.h"
+#include "scratch_carve.h"
 
 namespace pptk {
 namespace {
@@ -441,13 +442,9 @@ __global__ __launch_bounds__(kBlock) void dispatch_scatter_kernel(DispArgs a) {
   }
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
-size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
+// the derived counts of a call
 struct Layout {
   uint32_t nblk, cols;
-  size_t cnt, tot, total;
 };
 
 bool layout_of(uint64_t n, uint32_t nports, Layout *l) {
@@ -455,11 +452,16 @@ bool layout_of(uint64_t n, uint32_t nports, Layout *l) {
   const Cols col = {nports};
   l->nblk = (uint32_t)((n + kFrames - 1) / kFrames);
   l->cols = col.count(true);   // whether or not the call has per-frame lengths
-  size_t at = 0;
-  l->cnt = at, at += up256((size_t)l->cols * l->nblk * 4);
-  l->tot = at, at += up256((size_t)l->cols * 8);
-  l->total = at;
   return true;
+}
+
+// the scratch's arrays, in order: without a base the walk sizes the scratch,
+// with the scratch pointer it binds the arguments
+size_t carve(const Layout &l, void *base, DispArgs *a) {
+  Carve c(base, 256);
+  a->cnt = c.take<uint32_t>((size_t)l.cols * l.nblk);
+  a->tot = c.take<uint64_t>(l.cols);
+  return c.total();
 }
 
 }  // namespace
@@ -474,7 +476,8 @@ extern "C" void pptk_tx_dispatch_shape(uint32_t *block_frames, uint32_t *scan_wi
 
 extern "C" size_t pptk_tx_dispatch_scratch_bytes(uint64_t n, uint32_t nports) {
   Layout l;
-  return layout_of(n, nports, &l) ? l.total : 0;
+  DispArgs a;
+  return layout_of(n, nports, &l) ? carve(l, nullptr, &a) : 0;
 }
 
 extern "C" int pptk_tx_dispatch_device(struct pptk_rx_ctx *c, const struct pptk_dispatch *d,
@@ -487,9 +490,10 @@ extern "C" int pptk_tx_dispatch_device(struct pptk_rx_ctx *c, const struct pptk_
   const int rc = pptk_dispatch_check(d);
   if (rc) return rc;
   Layout l;
+  DispArgs a;
   if (d->n) {
     if (!layout_of(d->n, d->nports, &l) || !d_scratch || ((uintptr_t)d_scratch & 255u) ||
-        scratch_bytes < l.total)
+        scratch_bytes < carve(l, d_scratch, &a))
       return -EINVAL;
   }
   DeviceScope dg(ctx_device(c));
@@ -500,12 +504,8 @@ extern "C" int pptk_tx_dispatch_device(struct pptk_rx_ctx *c, const struct pptk_
     if (e == hipSuccess) e = hipMemsetAsync(d->ports, 0, d->nports * sizeof(*d->ports), s);
     return hip_rc(e);
   }
-  uint8_t *base = (uint8_t *)d_scratch;
-  DispArgs a;
   a.d = *d;
   a.nblk = l.nblk;
-  a.cnt = (uint32_t *)(base + l.cnt);
-  a.tot = (uint64_t *)(base + l.tot);
   const bool bytes = d->len != nullptr;
   const Cols col = {d->nports};
   const dim3 blk(kBlock);

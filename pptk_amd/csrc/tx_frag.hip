@@ -19,6 +19,7 @@
 #include "block_scan.h"
 #include "frame_view.h"
 #include "rx_internal.h"
+#include "scratch_carve.h"
 
 namespace pptk {
 namespace {
@@ -30,12 +31,7 @@ constexpr int kTeam = 16;                   // lanes per source frame in the emi
 constexpr int kUnroll = 4;                  // team rounds whose loads are in flight together
 
 struct FragArgs {
-  const uint8_t *frames;
-  const uint64_t *off;   // nullable -> fixed stride
-  const uint16_t *len;   // nullable -> fixed_len
-  uint64_t stride;
-  uint64_t n;
-  uint32_t fixed_len;
+  FrameBatch fb;
   uint32_t mtu;
   uint8_t *out;
   uint64_t out_stride;
@@ -54,74 +50,54 @@ struct FragArgs {
   uint8_t *s_st;
 };
 
-constexpr uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
-
-struct ScratchLayout {
-  uint64_t info, tile, cnt, first, st, total;
-};
-ScratchLayout scratch_layout(uint64_t n) {
-  ScratchLayout l;
-  const uint64_t ntiles = (n + kTile - 1) / kTile;
-  l.info = 0;
-  l.tile = l.info + up16(n * 8);
-  l.cnt = l.tile + up16(ntiles * 8);
-  l.first = l.cnt + up16(n * 4);
-  l.st = l.first + up16(n * 4);
-  l.total = l.st + up16(n);
-  return l;
+// the scratch's arrays, in order: without a base the walk sizes the scratch,
+// with the scratch pointer it binds the arguments
+size_t carve(uint64_t n, void *base, FragArgs *a) {
+  Carve c(base, 16);
+  a->s_info = c.take<uint64_t>(n);
+  a->s_tile = c.take<uint64_t>((n + kTile - 1) / kTile);
+  a->s_cnt = c.take<uint32_t>(n);
+  a->s_first = c.take<uint32_t>(n);
+  a->s_st = c.take<uint8_t>(n);
+  return c.total();
 }
 
 // ---- plan ------------------------------------------------------------------
-// The subject test is the IPv4 branch of the receive transform's parse
-// (frame_view.h parse_frame): one optional 802.1Q tag, ethertype 0x0800,
-// version 4, 20 <= ihl <= tl, l2 + tl <= len.  A frame shorter than 14 bytes
-// is not read at all; every other read lies inside the frame.
+// The subject test is outer_ipv4 (copy16.h).
 __global__ __launch_bounds__(kTile) void frag_plan_kernel(FragArgs a) {
   __shared__ uint32_t wsum[kTile / 64];
   const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
   uint32_t st = 0, cnt = 0;
-  if (i < a.n) {
-    const uint64_t base = a.off ? a.off[i] : i * a.stride;
-    const uint32_t len = a.len ? a.len[i] : a.fixed_len;
-    const uintptr_t F = (uintptr_t)a.frames + base;
-    if (len >= 14 && len <= 65535) {
-      uint32_t et = (ld_u8(F + 12) << 8) | ld_u8(F + 13), l2 = 14;
-      if (et == 0x8100 && len >= 18) {
-        et = (ld_u8(F + 16) << 8) | ld_u8(F + 17);
-        l2 = 18;
-      }
-      if (et == 0x0800 && len >= l2 + 20) {
-        const uintptr_t ip = F + l2;
-        const uint32_t w0 = ld_le32(ip), w1 = ld_le32(ip + 4), w2 = ld_le32(ip + 8);
-        const uint32_t b0 = w0 & 0xffu, ihl = (b0 & 15u) * 4u;
-        const uint32_t tl = bswap16(w0 >> 16);
-        if ((b0 >> 4) == 4 && ihl >= 20 && tl >= ihl && l2 + tl <= len) {
-          st = PPTK_FRAG_ST_IPV4;
-          if (tl <= a.mtu) {
-            st |= PPTK_FRAG_ST_FITS;
-          } else {
-            // the header's one's-complement sum over little-endian halves
-            // (byte order does not matter to the fold); s0 leaves out the
-            // three fields every fragment rewrites: total length, flags +
-            // offset, checksum
-            uint32_t s0 = (w0 & 0xffffu) + (w1 & 0xffffu) + (w2 & 0xffffu) +
-                          halves(ld_le32(ip + 12)) + halves(ld_le32(ip + 16));
-            for (uint32_t k = 20; k < ihl; k += 4) s0 += halves(ld_le32(ip + k));
-            const uint32_t all = s0 + (w0 >> 16) + (w1 >> 16) + (w2 >> 16);
-            const uint32_t fw = bswap16(w1 >> 16);
-            if (fw & 0x4000u) st |= PPTK_FRAG_ST_DF;
-            if (fw & 0x3fffu) st |= PPTK_FRAG_ST_ISFRAG;
-            if (fold16(all) != 0xffffu) st |= PPTK_FRAG_ST_BADCKSUM;
-            if (st == PPTK_FRAG_ST_IPV4) {
-              st |= PPTK_FRAG_ST_DONE;
-              const uint32_t per = (a.mtu - ihl) & ~7u;
-              cnt = (tl - ihl + per - 1) / per;
-              // s0 holds the version byte, so its fold is 1..0xffff
-              a.s_info[i] = (uint64_t)bswap16(fold16(s0)) | ((uint64_t)tl << 16) |
-                            ((uint64_t)ihl << 32) | ((uint64_t)l2 << 40) |
-                            ((uint64_t)(fw & 0xc000u) << 48);
-            }
-          }
+  if (i < a.fb.n) {
+    const uintptr_t F = a.fb.addr(i);
+    OuterIpv4 o;
+    if (outer_ipv4(F, a.fb.len_at(i), &o)) {
+      const uint32_t l2 = o.l2, ihl = o.ihl, tl = o.tl, w0 = o.w0, w1 = o.w1, w2 = o.w2;
+      const uintptr_t ip = F + l2;
+      st = PPTK_FRAG_ST_IPV4;
+      if (tl <= a.mtu) {
+        st |= PPTK_FRAG_ST_FITS;
+      } else {
+        // the header's one's-complement sum over little-endian halves
+        // (byte order does not matter to the fold); s0 leaves out the
+        // three fields every fragment rewrites: total length, flags +
+        // offset, checksum
+        uint32_t s0 = (w0 & 0xffffu) + (w1 & 0xffffu) + (w2 & 0xffffu) +
+                      halves(ld_le32(ip + 12)) + halves(ld_le32(ip + 16));
+        for (uint32_t k = 20; k < ihl; k += 4) s0 += halves(ld_le32(ip + k));
+        const uint32_t all = s0 + (w0 >> 16) + (w1 >> 16) + (w2 >> 16);
+        const uint32_t fw = bswap16(w1 >> 16);
+        if (fw & 0x4000u) st |= PPTK_FRAG_ST_DF;
+        if (fw & 0x3fffu) st |= PPTK_FRAG_ST_ISFRAG;
+        if (fold16(all) != 0xffffu) st |= PPTK_FRAG_ST_BADCKSUM;
+        if (st == PPTK_FRAG_ST_IPV4) {
+          st |= PPTK_FRAG_ST_DONE;
+          const uint32_t per = (a.mtu - ihl) & ~7u;
+          cnt = (tl - ihl + per - 1) / per;
+          // s0 holds the version byte, so its fold is 1..0xffff
+          a.s_info[i] = (uint64_t)bswap16(fold16(s0)) | ((uint64_t)tl << 16) |
+                        ((uint64_t)ihl << 32) | ((uint64_t)l2 << 40) |
+                        ((uint64_t)(fw & 0xc000u) << 48);
         }
       }
     }
@@ -131,7 +107,7 @@ __global__ __launch_bounds__(kTile) void frag_plan_kernel(FragArgs a) {
   // exclusive prefix inside the tile (at most 256 * 8190 slots: 32 bits)
   uint32_t total;
   const uint32_t before = block_excl_scan<kTile / 64, uint32_t>(cnt, wsum, &total);
-  if (i < a.n) a.s_first[i] = before;
+  if (i < a.fb.n) a.s_first[i] = before;
   if (threadIdx.x == 0) a.s_tile[blockIdx.x] = total;
 }
 
@@ -161,7 +137,7 @@ __global__ __launch_bounds__(kScanThreads) void frag_scan_kernel(FragArgs a, uin
 // ---- apply -----------------------------------------------------------------
 __global__ __launch_bounds__(kTile) void frag_apply_kernel(FragArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
-  if (i >= a.n) return;
+  if (i >= a.fb.n) return;
   const uint64_t first = a.s_tile[blockIdx.x] + a.s_first[i];
   const uint32_t cnt = a.s_cnt[i];
   uint32_t st = a.s_st[i];
@@ -182,14 +158,14 @@ __global__ __launch_bounds__(kTile) void frag_apply_kernel(FragArgs a) {
 // (the re-aligning chunk loads and the field helpers: copy16.h)
 __device__ __forceinline__ void emit_frame(const FragArgs &a, uint64_t i, uint32_t t,
                                            LDS_AS u32x4 *hds) {
-  const uint64_t base = a.off ? a.off[i] : i * a.stride;
+  const uint64_t base = a.fb.base(i);
   const uint64_t info = a.s_info[i];
   const uint32_t first = a.s_first[i], count = a.s_cnt[i];
   const uint32_t s0 = (uint32_t)info & 0xffffu, tl = (uint32_t)(info >> 16) & 0xffffu;
   const uint32_t ihl = (uint32_t)(info >> 32) & 0xffu, l2 = (uint32_t)(info >> 40) & 0xffu;
   const uint32_t fkeep = (uint32_t)(info >> 48);   // the reserved bit (DF is clear)
   const uint32_t H = l2 + ihl, datamax = tl - ihl, per = (a.mtu - ihl) & ~7u;
-  const uintptr_t F = (uintptr_t)a.frames + base;
+  const uintptr_t F = (uintptr_t)a.fb.frames + base;
 
   // lengths and source indices of the frame's slots, a run of `count`
   for (uint32_t j = t; j < count; j += kTeam) {
@@ -265,10 +241,10 @@ __global__ __launch_bounds__(256) void frag_emit_kernel(FragArgs a) {
   const uint32_t t = threadIdx.x & (kTeam - 1);
   const uint64_t team = ((uint64_t)blockIdx.x * 256u + threadIdx.x) / kTeam;
   const uint64_t step = (uint64_t)gridDim.x * 256u;
-  for (uint64_t g = team * kTeam; g < a.n; g += step) {
+  for (uint64_t g = team * kTeam; g < a.fb.n; g += step) {
     // each lane looks at one of the team's 16 frames; the team then walks
     // those that are to be written
-    const uint32_t st = g + t < a.n ? a.s_st[g + t] : 0u;
+    const uint32_t st = g + t < a.fb.n ? a.s_st[g + t] : 0u;
     const bool go = (st & (PPTK_FRAG_ST_DONE | PPTK_FRAG_ST_NOROOM)) == PPTK_FRAG_ST_DONE;
     uint32_t mask = (uint32_t)(__ballot(go) >> (threadIdx.x & 48u)) & 0xffffu;
     while (mask) {
@@ -279,15 +255,14 @@ __global__ __launch_bounds__(256) void frag_emit_kernel(FragArgs a) {
   }
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
 }  // namespace
 }  // namespace pptk
 
 using namespace pptk;
 
 extern "C" size_t pptk_ip_fragment_scratch_bytes(uint64_t n) {
-  return (size_t)scratch_layout(n).total + 64;
+  FragArgs a;
+  return carve(n, nullptr, &a) + 64;
 }
 
 extern "C" int pptk_ip_fragment_device(struct pptk_rx_ctx *c, const uint8_t *d_frames,
@@ -298,26 +273,19 @@ extern "C" int pptk_ip_fragment_device(struct pptk_rx_ctx *c, const uint8_t *d_f
                                        uint32_t *d_first, uint32_t *d_count, uint8_t *d_status,
                                        uint64_t *d_totals, void *d_scratch, void *stream) {
   if (!c || !d_totals || n > kMaxFrames || mtu < 68 || mtu > 65535) return -EINVAL;
-  if (((uintptr_t)d_out & 15u) || (out_stride & 15u) || out_stride < up16(18u + (uint64_t)mtu) ||
-      out_cap > 0xffffffffull || (!d_out && out_cap))
+  if (((uintptr_t)d_out & 15u) || (out_stride & 15u) ||
+      out_stride < ((18u + (uint64_t)mtu + 15u) & ~15ull) || out_cap > 0xffffffffull ||
+      (!d_out && out_cap))
     return -EINVAL;
-  if (n && (!d_frames || !d_scratch || ((uintptr_t)d_scratch & 15u) ||
-            (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535)))
-    return -EINVAL;
+  if (n && (!d_scratch || ((uintptr_t)d_scratch & 15u))) return -EINVAL;
+  if (!frame_batch_ok(d_frames, d_off, d_len, stride, fixed_len, n)) return -EINVAL;
   DeviceScope dg(ctx_device(c));
   if (!dg.ok) return -EIO;
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) return hip_rc(hipMemsetAsync(d_totals, 0, 2 * sizeof(uint64_t), s));
 
-  const ScratchLayout l = scratch_layout(n);
-  uint8_t *sc = (uint8_t *)d_scratch;
   FragArgs a;
-  a.frames = d_frames;
-  a.off = d_off;
-  a.len = d_len;
-  a.stride = stride;
-  a.n = n;
-  a.fixed_len = fixed_len;
+  a.fb = {d_frames, d_off, d_len, stride, n, fixed_len};
   a.mtu = mtu;
   a.out = d_out;
   a.out_stride = out_stride;
@@ -328,11 +296,7 @@ extern "C" int pptk_ip_fragment_device(struct pptk_rx_ctx *c, const uint8_t *d_f
   a.count = d_count;
   a.status = d_status;
   a.totals = d_totals;
-  a.s_info = (uint64_t *)(sc + l.info);
-  a.s_tile = (uint64_t *)(sc + l.tile);
-  a.s_cnt = (uint32_t *)(sc + l.cnt);
-  a.s_first = (uint32_t *)(sc + l.first);
-  a.s_st = sc + l.st;
+  (void)carve(n, d_scratch, &a);
   const uint32_t ntiles = (uint32_t)((n + kTile - 1) / kTile);
   hipLaunchKernelGGL(frag_plan_kernel, dim3(ntiles), dim3(kTile), 0, s, a);
   hipLaunchKernelGGL(frag_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, a, ntiles);

@@ -67,12 +67,12 @@ struct LaneFrame {
 template <int SLOT>
 __device__ __forceinline__ LaneFrame load_frame(const HdrBatch &b, uint64_t i,
                                                 LDS_AS uint8_t *slot) {
-  const uint64_t base = b.off ? b.off[i] : i * b.stride;
-  const uint32_t len = b.len ? b.len[i] : b.fixed_len;
+  const uint64_t base = b.fb.base(i);
+  const uint32_t len = b.fb.len_at(i);
   const int m = (int)(base & 15);
   const int nch = max((m + (int)len + 15) >> 4, 1);
-  park_chunks<SLOT>(slot, (const u32x4 *)(b.frames + (base - (uint64_t)m)), nch);
-  return {base, len, m, {slot, (const GLB_AS uint8_t *)b.frames + base, m, SLOT - m}};
+  park_chunks<SLOT>(slot, (const u32x4 *)(b.fb.frames + (base - (uint64_t)m)), nch);
+  return {base, len, m, {slot, (const GLB_AS uint8_t *)b.fb.frames + base, m, SLOT - m}};
 }
 
 // The write-back of one chunk of a patched slot.  `row` is the frame's first
@@ -146,7 +146,7 @@ constexpr int RW_SLOT = 64;
 __global__ __launch_bounds__(256) void rx_rewrite_kernel(RewriteKArgs a) {
   LDS_AS uint8_t *slot = lane_slot<RW_SLOT>();
   const uint64_t step = (uint64_t)gridDim.x * 256u;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.b.n; i += step) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.b.fb.n; i += step) {
     const uint64_t j = a.idx ? (uint64_t)a.idx[i] : (a.rw_one ? 0u : i);
     if (a.idx && j >= a.rw_count) {   // no flow: the frame is not even read
       if (a.b.status) a.b.status[i] = (uint8_t)PPTK_RW_ST_NOFLOW;
@@ -242,7 +242,7 @@ constexpr int MSS_SLOT = 128;
 __global__ __launch_bounds__(256) void rx_mss_kernel(MssKArgs a) {
   LDS_AS uint8_t *slot = lane_slot<MSS_SLOT>();
   const uint64_t step = (uint64_t)gridDim.x * 256u;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.b.n; i += step) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.b.fb.n; i += step) {
     const LaneFrame fr = load_frame<MSS_SLOT>(a.b, i, slot);
     const uint64_t base = fr.base;
     const uint32_t len = fr.len;
@@ -446,7 +446,7 @@ constexpr int SEQ_SLOT = 128;
 __global__ __launch_bounds__(256) void rx_seq_kernel(SeqKArgs a) {
   LDS_AS uint8_t *slot = lane_slot<SEQ_SLOT>();
   const uint64_t step = (uint64_t)gridDim.x * 256u;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.b.n; i += step) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.b.fb.n; i += step) {
     const uint64_t j = a.idx ? (uint64_t)a.idx[i] : (a.xl_one ? 0u : i);
     if (j >= a.xl_count) {   // no flow: the frame is not even read
       if (a.b.status) a.b.status[i] = (uint8_t)PPTK_SEQ_ST_NOFLOW;

@@ -42,11 +42,7 @@ constexpr int kTeamAny = 16;
 #endif
 
 struct EncapArgs {
-  const uint8_t *frames;
-  const uint64_t *off;   // nullable -> fixed stride
-  const uint16_t *len;   // nullable -> fixed_len
-  uint64_t stride;
-  uint64_t n;
+  FrameBatch fb;
   const pptk_tunnel *tun;
   uint64_t tun_count;
   const uint32_t *idx;   // nullable -> tun[tun_one ? 0 : i]
@@ -54,21 +50,15 @@ struct EncapArgs {
   uint64_t out_stride;
   uint16_t *out_len;     // nullable
   uint8_t *status;       // nullable
-  uint32_t fixed_len;
   uint32_t tun_one;
   uint32_t id_base;
 };
 
 struct DecapArgs {
-  const uint8_t *frames;
-  const uint64_t *off;
-  const uint16_t *len;
-  uint64_t stride;
-  uint64_t n;
+  FrameBatch fb;
   uint64_t *in_off;      // nullable
   uint16_t *in_len;      // nullable
   uint8_t *status;       // nullable
-  uint32_t fixed_len;
 };
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void tunnel_encap_kernel(EncapArgs a) {
   const uint32_t t = threadIdx.x & (T - 1);
   const uint64_t team = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) / T;
   const uint64_t nteams = (uint64_t)gridDim.x * (kBlock / T);
-  for (uint64_t i = team; i < a.n; i += nteams) {
+  for (uint64_t i = team; i < a.fb.n; i += nteams) {
     const uint64_t ti = a.idx ? (uint64_t)a.idx[i] : (a.tun_one ? 0 : i);
     uint32_t st = 0, len = 0;
     u32x4 ta = {0, 0, 0, 0}, tb = {0, 0, 0, 0};
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void tunnel_encap_kernel(EncapArgs a) {
       if ((tb.z & ~(PPTK_TUN_DF | PPTK_TUN_ID_SEQ)) || tb.w) {
         st = PPTK_TUN_ST_BADTUN;
       } else {
-        len = a.len ? a.len[i] : a.fixed_len;
+        len = a.fb.len_at(i);
         if (len < 14) {
           st = PPTK_TUN_ST_RUNT;
         } else {
@@ -122,8 +112,7 @@ __global__ __launch_bounds__(kBlock) void tunnel_encap_kernel(EncapArgs a) {
     }
     if (st != PPTK_TUN_ST_DONE) continue;
 
-    const uint64_t base = a.off ? a.off[i] : i * a.stride;
-    const uintptr_t F = (uintptr_t)a.frames + base;
+    const uintptr_t F = a.fb.addr(i);
     uint8_t *slot = a.out + i * a.out_stride;
     const uint32_t src_be = bswap32(ta.w), dst_be = bswap32(tb.x);
 
@@ -180,49 +169,38 @@ __global__ __launch_bounds__(kBlock) void tunnel_encap_kernel(EncapArgs a) {
   }
 }
 
-// The outer subject test is frag_plan_kernel's (tx_frag.hip): a frame shorter
-// than 14 bytes is not read at all; every other read lies inside the frame.
+// The outer subject test is outer_ipv4 (copy16.h).
 __global__ __launch_bounds__(kBlock) void tunnel_decap_kernel(DecapArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= a.n) return;
-  const uint64_t base = a.off ? a.off[i] : i * a.stride;
-  const uint32_t len = a.len ? a.len[i] : a.fixed_len;
-  const uintptr_t F = (uintptr_t)a.frames + base;
+  if (i >= a.fb.n) return;
+  const uint64_t base = a.fb.base(i);
+  const uint32_t len = a.fb.len_at(i);
+  const uintptr_t F = (uintptr_t)a.fb.frames + base;
   uint32_t st = 0, in_len = 0;
   uint64_t in_off = base;
-  if (len >= 14 && len <= 65535) {
-    uint32_t et = (ld_u8(F + 12) << 8) | ld_u8(F + 13), l2 = 14;
-    if (et == 0x8100 && len >= 18) {
-      et = (ld_u8(F + 16) << 8) | ld_u8(F + 17);
-      l2 = 18;
-    }
-    if (et == 0x0800 && len >= l2 + 20) {
-      const uintptr_t ip = F + l2;
-      const uint32_t w0 = ld_le32(ip), w1 = ld_le32(ip + 4), w2 = ld_le32(ip + 8);
-      const uint32_t b0 = w0 & 0xffu, ihl = (b0 & 15u) * 4u;
-      const uint32_t tl = bswap16(w0 >> 16);
-      if ((b0 >> 4) == 4 && ihl >= 20 && tl >= ihl && l2 + tl <= len) {
-        st = PPTK_DECAP_ST_IPV4;
-        if (((w2 >> 8) & 0xffu) == 47u) {
-          uint32_t sum = halves(w0) + halves(w1) + halves(w2) + halves(ld_le32(ip + 12)) +
-                         halves(ld_le32(ip + 16));
-          for (uint32_t k = 20; k < ihl; k += 4) sum += halves(ld_le32(ip + k));
-          if (fold16(sum) != 0xffffu) st |= PPTK_DECAP_ST_BADCKSUM;
-          if (bswap16(w1 >> 16) & 0x3fffu) {
-            st |= PPTK_DECAP_ST_ISFRAG;
-          } else if (tl - ihl < 4) {
-            st |= PPTK_DECAP_ST_SHORT;
-          } else {
-            st |= PPTK_DECAP_ST_GRE;
-            const uint32_t g = ld_le32(ip + ihl);
-            if (g & 0xffffu) st |= PPTK_DECAP_ST_GREOPT;
-            if ((g >> 16) != 0x5865u) st |= PPTK_DECAP_ST_PTYPE;
-            if (st == (PPTK_DECAP_ST_IPV4 | PPTK_DECAP_ST_GRE)) {
-              st |= PPTK_DECAP_ST_OK;
-              in_off = base + l2 + ihl + 4;
-              in_len = tl - ihl - 4;
-            }
-          }
+  OuterIpv4 o;
+  if (outer_ipv4(F, len, &o)) {
+    const uint32_t l2 = o.l2, ihl = o.ihl, tl = o.tl, w0 = o.w0, w1 = o.w1, w2 = o.w2;
+    const uintptr_t ip = F + l2;
+    st = PPTK_DECAP_ST_IPV4;
+    if (((w2 >> 8) & 0xffu) == 47u) {
+      uint32_t sum = halves(w0) + halves(w1) + halves(w2) + halves(ld_le32(ip + 12)) +
+                     halves(ld_le32(ip + 16));
+      for (uint32_t k = 20; k < ihl; k += 4) sum += halves(ld_le32(ip + k));
+      if (fold16(sum) != 0xffffu) st |= PPTK_DECAP_ST_BADCKSUM;
+      if (bswap16(w1 >> 16) & 0x3fffu) {
+        st |= PPTK_DECAP_ST_ISFRAG;
+      } else if (tl - ihl < 4) {
+        st |= PPTK_DECAP_ST_SHORT;
+      } else {
+        st |= PPTK_DECAP_ST_GRE;
+        const uint32_t g = ld_le32(ip + ihl);
+        if (g & 0xffffu) st |= PPTK_DECAP_ST_GREOPT;
+        if ((g >> 16) != 0x5865u) st |= PPTK_DECAP_ST_PTYPE;
+        if (st == (PPTK_DECAP_ST_IPV4 | PPTK_DECAP_ST_GRE)) {
+          st |= PPTK_DECAP_ST_OK;
+          in_off = base + l2 + ihl + 4;
+          in_len = tl - ihl - 4;
         }
       }
     }
@@ -232,19 +210,10 @@ __global__ __launch_bounds__(kBlock) void tunnel_decap_kernel(DecapArgs a) {
   if (a.status) a.status[i] = (uint8_t)st;
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -EIO; }
-
 template <int T>
 void launch_encap(const EncapArgs &a, hipStream_t s) {
-  const uint64_t per_block = kBlock / T;
-  const uint64_t blocks = (a.n + per_block - 1) / per_block;
-  hipLaunchKernelGGL(tunnel_encap_kernel<T>, dim3((uint32_t)(blocks < kMaxGrid ? blocks : kMaxGrid)),
+  hipLaunchKernelGGL(tunnel_encap_kernel<T>, dim3(capped_grid(a.fb.n, kBlock / T, kMaxGrid)),
                      dim3(kBlock), 0, s, a);
-}
-
-bool bad_layout(const uint8_t *d_frames, const uint64_t *d_off, const uint16_t *d_len,
-                uint64_t stride, uint32_t fixed_len, uint64_t n) {
-  return n && (!d_frames || (!d_off && stride == 0 && n > 1) || (!d_len && fixed_len > 65535));
 }
 
 }  // namespace
@@ -264,16 +233,12 @@ extern "C" int pptk_tunnel_encap_device(struct pptk_rx_ctx *c, const uint8_t *d_
       (!d_idx && tun_count != 1 && tun_count != n))
     return -EINVAL;
   if (((uintptr_t)d_out & 15u) || (out_stride & 15u) || (n && !d_out)) return -EINVAL;
-  if (bad_layout(d_frames, d_off, d_len, stride, fixed_len, n)) return -EINVAL;
+  if (!frame_batch_ok(d_frames, d_off, d_len, stride, fixed_len, n)) return -EINVAL;
   DeviceScope dg(ctx_device(c));
   if (!dg.ok) return -EIO;
   if (n == 0) return 0;
   EncapArgs a;
-  a.frames = d_frames;
-  a.off = d_off;
-  a.len = d_len;
-  a.stride = stride;
-  a.n = n;
+  a.fb = {d_frames, d_off, d_len, stride, n, fixed_len};
   a.tun = d_tun;
   a.tun_count = tun_count;
   a.idx = d_idx;
@@ -281,7 +246,6 @@ extern "C" int pptk_tunnel_encap_device(struct pptk_rx_ctx *c, const uint8_t *d_
   a.out_stride = out_stride;
   a.out_len = d_out_len;
   a.status = d_status;
-  a.fixed_len = fixed_len;
   a.tun_one = tun_count == 1;
   a.id_base = id_base;
   hipStream_t s = (hipStream_t)stream;
@@ -307,22 +271,17 @@ extern "C" int pptk_tunnel_decap_device(struct pptk_rx_ctx *c, const uint8_t *d_
                                         uint64_t stride, uint32_t fixed_len, uint64_t n,
                                         uint64_t *d_in_off, uint16_t *d_in_len,
                                         uint8_t *d_status, void *stream) {
-  if (!c || bad_layout(d_frames, d_off, d_len, stride, fixed_len, n)) return -EINVAL;
+  if (!c || !frame_batch_ok(d_frames, d_off, d_len, stride, fixed_len, n)) return -EINVAL;
   const uint64_t blocks = (n + kBlock - 1) / kBlock;
   if (blocks > 0x7fffffffull) return -EINVAL;
   DeviceScope dg(ctx_device(c));
   if (!dg.ok) return -EIO;
   if (n == 0) return 0;
   DecapArgs a;
-  a.frames = d_frames;
-  a.off = d_off;
-  a.len = d_len;
-  a.stride = stride;
-  a.n = n;
+  a.fb = {d_frames, d_off, d_len, stride, n, fixed_len};
   a.in_off = d_in_off;
   a.in_len = d_in_len;
   a.status = d_status;
-  a.fixed_len = fixed_len;
   hipLaunchKernelGGL(tunnel_decap_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0,
                      (hipStream_t)stream, a);
   return hip_rc(hipGetLastError());
