@@ -15,14 +15,16 @@ HIP_SRCS := pptk_amd/csrc/rx_kernel.hip pptk_amd/csrc/rx_bin.hip pptk_amd/csrc/r
             pptk_amd/csrc/rx_capi.hip pptk_amd/csrc/rx_comm.hip pptk_amd/csrc/rx_ring.hip \
             pptk_amd/csrc/tx_frag.hip pptk_amd/csrc/tx_tunnel.hip pptk_amd/csrc/tx_hdr.hip \
             pptk_amd/csrc/rx_flow.hip pptk_amd/csrc/rx_flowstat.hip pptk_amd/csrc/rx_flowlearn.hip \
-            pptk_amd/csrc/rx_host.hip pptk_amd/csrc/ip_reass.hip pptk_amd/csrc/tx_dispatch.hip
+            pptk_amd/csrc/rx_host.hip pptk_amd/csrc/ip_reass.hip pptk_amd/csrc/tx_dispatch.hip \
+            pptk_amd/csrc/tx_gather.hip
 C_SRCS := pptk_amd/csrc/host/ipcksum.c pptk_amd/csrc/host/hashseed.c pptk_amd/csrc/host/tcpopt.c \
           pptk_amd/csrc/host/iphash.c pptk_amd/csrc/host/timerlink.c pptk_amd/csrc/host/ipfrag.c \
           pptk_amd/csrc/host/tcpseq.c pptk_amd/csrc/host/tunnel.c pptk_amd/csrc/host/flowtab.c \
-          pptk_amd/csrc/host/flowlearn.c pptk_amd/csrc/host/ipreass.c pptk_amd/csrc/host/dispatch.c
+          pptk_amd/csrc/host/flowlearn.c pptk_amd/csrc/host/ipreass.c pptk_amd/csrc/host/dispatch.c \
+          pptk_amd/csrc/host/gather.c
 HDRS := $(wildcard include/*.h) pptk_amd/csrc/rx_internal.h pptk_amd/csrc/copy16.h \
         pptk_amd/csrc/frame_view.h pptk_amd/csrc/flowtab.h pptk_amd/csrc/host_plan.h \
-        pptk_amd/csrc/dispatch_check.h pptk_amd/csrc/block_scan.h \
+        pptk_amd/csrc/dispatch_check.h pptk_amd/csrc/gather_check.h pptk_amd/csrc/block_scan.h \
         pptk_amd/csrc/scratch_carve.h pptk_amd/csrc/host/outer_ipv4.h
 HIP_OBJS := $(patsubst pptk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
 C_OBJS := $(patsubst pptk_amd/csrc/host/%.c,$(OBJDIR)/host/%.o,$(C_SRCS))
@@ -70,7 +72,7 @@ abvariant:
 	  HIPFLAGS="$(HIPFLAGS) $(DEFS)" build/ab_$(NAME)/libpptkrx.so
 
 # the kernel files' assembly and resource tables (build/asm/<file>.resource.txt)
-ASM_SRCS := rx_kernel tx_hdr rx_flowstat rx_flowlearn tx_dispatch ip_reass tx_frag tx_tunnel rx_flow
+ASM_SRCS := rx_kernel tx_hdr rx_flowstat rx_flowlearn tx_dispatch ip_reass tx_frag tx_tunnel rx_flow tx_gather
 asm: $(HIP_SRCS)
 	@mkdir -p build/asm
 	cd build/asm && for f in $(ASM_SRCS); do $(HIPCC) $(HIPFLAGS) -I../../include -c ../../pptk_amd/csrc/$$f.hip -save-temps -o $$f.o -Rpass-analysis=kernel-resource-usage 2> $$f.resource.txt; done; true

@@ -1222,7 +1222,8 @@ void pptk_flow_learn_shape(uint32_t *block_frames, uint32_t *scan_width);
  *
  * Out of scope: a MAC-keyed table and MAC learning (the caller supplies the
  * code per frame, or per flow through the 5-tuple table); copying frame bytes
- * into per-port buffers (the lists describe frames in place); VLAN-scoped
+ * into per-port buffers (the lists describe frames in place; "Egress gather"
+ * below packs them); VLAN-scoped
  * flooding or multicast groups beyond "all but ingress"; more than 64 ports;
  * carrying the fragmenter's d_out_src through (the caller dispatches the
  * slots as a batch of their own); a host ldp_packet[] form. */
@@ -1272,6 +1273,127 @@ int pptk_tx_dispatch_device(struct pptk_rx_ctx *ctx, const struct pptk_dispatch 
                             void *d_scratch, size_t scratch_bytes, void *stream);
 int pptk_tx_dispatch_host(const struct pptk_dispatch *d);
 void pptk_tx_dispatch_shape(uint32_t *block_frames, uint32_t *scan_width);
+
+/* Egress gather: each port's tx list packed into contiguous buffers.  The
+ * dispatch above says which frames leave through which port, as entries that
+ * name frames in place -- scattered over the whole batch, a flood frame named
+ * by several runs.  The reference ends the same loop with the copy: per port,
+ * ldp_out_inject copies every packet of the port's output table into the next
+ * tx slot (ldp/ldpnetmap.c:68, ldp/ldpdpdk.c:256, called from
+ * ldp/ldpswitch.c:311-318).  Here one call copies the frames of every run back
+ * to back into `out`, one region per port, so that a caller whose NIC sits
+ * behind the host downloads one range per port:
+ *   rx -> pptk_flow_lookup_device -> pptk_tx_dispatch_device ->
+ *      pptk_tx_gather_device(list, d_entries = &dispatch hdr.written, runs =
+ *      dispatch ports) -> download ports -> per port p: one download of
+ *      out[start, start + bytes) -> inject pk_off / pk_len of the run.
+ *
+ * pptk_tx_gather_host is the CPU statement; the device call equals it byte for
+ * byte.  Considered entries: E = max_entries, or min(max_entries, *d_entries)
+ * where d_entries is given (a device word on the device call, read on the
+ * device: the call never synchronises with the host); with `runs` E is also
+ * cut at the end of the last run, so every considered entry lies in a run.
+ * Port p's entries are [runs[p].start, runs[p].start + runs[p].count) cut at
+ * E; runs[].bytes and runs[].flooded are not read.  The runs must lie back to
+ * back from 0, as dispatch writes them (runs[0].start == 0, runs[p + 1].start
+ * == runs[p].start + runs[p].count, no sum wrapping); otherwise hdr.status =
+ * PPTK_GATHER_ST_BADRUNS, every other word of hdr and of ports is 0, and
+ * nothing else is written.  Null runs (nports == 1) make one region of every
+ * entry.
+ *
+ * Entry g names frame i = list ? list[g] : g.  Its length is L = len ? len[i]
+ * : fixed_len, its slot round_up(L, 16) bytes.  A bad entry (i >= n) has L = 0
+ * and counts in hdr.bad; nothing of the source is read for it.  Region 0
+ * starts at 0, region p + 1 at round_up(start_p + the slot bytes of all
+ * considered entries of p, 256), whether or not they fit.  pk_off[g] is the
+ * region start plus the slots of the run's earlier entries, pk_len[g] is L;
+ * both are written for every considered entry and for no other.  hdr.need is
+ * the end of the last region's slots.  Entry g is packed iff pk_off[g] + slot
+ * <= out_cap; offsets never decrease in g, so the packed entries are a prefix
+ * of hdr.packed entries, and ports[p].packed / ports[p].bytes count that
+ * prefix inside each run.  For a packed entry out[pk_off, pk_off + L) holds
+ * the frame's bytes and [L, slot) zeros.  No other byte of out is written:
+ * not the padding between regions, nothing from an unpacked entry on, nothing
+ * past out_cap.  Of the source nothing outside the aligned 16-byte chunks of
+ * [frame, frame + L) is read.  A flood frame named by several entries is
+ * copied once per entry.  out must not overlap the source batch (not
+ * checked).  out null with out_cap 0 is legal, the call then only counts;
+ * pk_off and pk_len are nullable.  max_entries == 0 writes a zero header and
+ * nports zero port entries and launches no more than that (the runs are not
+ * looked at).  The padding members are ignored.
+ *
+ * -EINVAL: a null ctx (device call), g, ports or hdr; nports 0 or above
+ * PPTK_PORT_MAX, or runs null with nports != 1; a source batch no batch op
+ * accepts (n > 0 with null frames, neither off nor stride while n > 1, or
+ * fixed_len > 65535 without len); max_entries >= 2^32 or n >= 2^32; out null
+ * with out_cap > 0, or out not 256-byte aligned; list not 4-byte, off,
+ * pk_off, runs, ports, hdr or d_entries not 8-byte, len or pk_len not 2-byte
+ * aligned; and, on the device call with max_entries > 0, a scratch that is
+ * null, not 256-byte aligned or smaller than
+ * pptk_tx_gather_scratch_bytes(max_entries, nports) (0 for max_entries = 0 or
+ * arguments the call would reject).
+ *
+ * The device call reads `g` before it returns (the struct itself is host
+ * memory, its arrays device memory), clears what it needs of the scratch
+ * itself, is asynchronous on `stream` (launches ordered by the stream alone)
+ * and must not share a scratch with a call in flight on another stream.  The
+ * result is the same for any grid: no atomic operation takes part in an
+ * offset, and every loop's trip count is a constant, a kernel argument or a
+ * device value clamped by one.  pptk_tx_gather_shape reports the built
+ * kernels: the entries of one workgroup of the count and copy passes
+ * (block_entries) and the block sums a scan workgroup takes per round
+ * (scan_width).  Results do not depend on it.
+ *
+ * Out of scope: headroom or a per-frame prepend in the slot; slot alignments
+ * other than 16; a host ldp_packet[] form, or the download itself; writing
+ * into netmap or DPDK rings; a MAC-keyed table; a gather straight from the
+ * fragmenter's d_out_src. */
+#define PPTK_GATHER_SLOT_ALIGN   16u    /* every packed frame starts at a multiple */
+#define PPTK_GATHER_REGION_ALIGN 256u   /* every port's region starts at a multiple */
+#define PPTK_GATHER_ST_BADRUNS   1u     /* hdr.status: runs not back to back from 0 */
+
+struct pptk_gather_port {     /* 32 bytes, one per port, device memory */
+  uint64_t start;             /* byte offset of the region in out, multiple of 256 */
+  uint64_t bytes;             /* slot bytes of the run's packed entries            */
+  uint64_t entries;           /* considered entries of the run                     */
+  uint64_t packed;            /* of them packed (a prefix of the run)              */
+};
+struct pptk_gather_hdr {      /* 64 bytes, 8-byte aligned */
+  uint64_t entries;           /* considered entries                                */
+  uint64_t packed;            /* entries g < packed lie in out                     */
+  uint64_t need;              /* out_cap at which every considered entry is packed */
+  uint64_t bytes;             /* sum of ports[p].bytes                             */
+  uint64_t frame_bytes;       /* sum of the frame lengths of the packed entries    */
+  uint64_t bad;               /* considered entries with list[g] >= n              */
+  uint64_t status;            /* 0 or PPTK_GATHER_ST_BADRUNS                       */
+  uint64_t reserved;          /* 0 */
+};
+struct pptk_gather {          /* arguments, host and device call alike; 136 bytes */
+  const uint8_t *frames;      /* the source batch, as every batch op takes it      */
+  const uint64_t *off;        /* nullable: frame i lies at i * stride              */
+  const uint16_t *len;        /* nullable: every frame is fixed_len long           */
+  uint64_t stride;
+  uint32_t fixed_len;
+  uint32_t pad0;
+  uint64_t n;                 /* frames of the batch                               */
+  const uint32_t *list;       /* nullable: entry g is frame g                      */
+  uint64_t max_entries;       /* host bound: sizes grids and scratch               */
+  const uint64_t *d_entries;  /* nullable word, e.g. &dispatch hdr.written         */
+  const struct pptk_dispatch_port *runs;   /* nullable: one region, nports == 1    */
+  uint32_t nports;            /* 1 .. PPTK_PORT_MAX                                */
+  uint32_t pad1;
+  uint8_t *out;               /* nullable with out_cap 0: count only               */
+  uint64_t out_cap;
+  uint64_t *pk_off;           /* nullable, max_entries each                        */
+  uint16_t *pk_len;
+  struct pptk_gather_port *ports;   /* nports entries */
+  struct pptk_gather_hdr *hdr;
+};
+size_t pptk_tx_gather_scratch_bytes(uint64_t max_entries, uint32_t nports);
+int pptk_tx_gather_device(struct pptk_rx_ctx *ctx, const struct pptk_gather *g,
+                          void *d_scratch, size_t scratch_bytes, void *stream);
+int pptk_tx_gather_host(const struct pptk_gather *g);
+void pptk_tx_gather_shape(uint32_t *block_entries, uint32_t *scan_width);
 
 /* Tuning: force kernel variant `variant` (0 .. pptk_rx_variant_count()-1)
  * and/or memory-policy flags for every later batch of this context; -1

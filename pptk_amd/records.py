@@ -93,6 +93,14 @@ DISPATCH_HDR_DTYPE = np.dtype([("total", "<u8"), ("written", "<u8"), ("unicast",
                                ("hairpin", "<u8"), ("reserved", "<u8")])
 assert DISPATCH_PORT_DTYPE.itemsize == 32 and DISPATCH_HDR_DTYPE.itemsize == 64
 PORT_MAX, PORT_FLOOD, PORT_DROP = 64, 0xFF, 0xFE
+# struct pptk_gather_port / pptk_gather_hdr (include/pptk_rx.h "Egress gather")
+GATHER_PORT_DTYPE = np.dtype([("start", "<u8"), ("bytes", "<u8"), ("entries", "<u8"),
+                              ("packed", "<u8")])
+GATHER_HDR_DTYPE = np.dtype([("entries", "<u8"), ("packed", "<u8"), ("need", "<u8"),
+                             ("bytes", "<u8"), ("frame_bytes", "<u8"), ("bad", "<u8"),
+                             ("status", "<u8"), ("reserved", "<u8")])
+assert GATHER_PORT_DTYPE.itemsize == 32 and GATHER_HDR_DTYPE.itemsize == 64
+GATHER_SLOT_ALIGN, GATHER_REGION_ALIGN, GATHER_ST_BADRUNS = 16, 256, 1
 
 REC32_DTYPE = np.dtype([
     ("flow_hash", "<u8"),

@@ -181,8 +181,23 @@ class Dispatch(ctypes.Structure):
                 ("ports", ctypes.c_void_p), ("hdr", ctypes.c_void_p)]
 
 
+class Gather(ctypes.Structure):
+    """struct pptk_gather (include/pptk_rx.h "Egress gather"): the arguments of
+    pptk_tx_gather_device / _host; the pointers are addresses."""
+    _fields_ = [("frames", ctypes.c_void_p), ("off", ctypes.c_void_p), ("len", ctypes.c_void_p),
+                ("stride", ctypes.c_uint64), ("fixed_len", ctypes.c_uint32),
+                ("pad0", ctypes.c_uint32), ("n", ctypes.c_uint64), ("list", ctypes.c_void_p),
+                ("max_entries", ctypes.c_uint64), ("d_entries", ctypes.c_void_p),
+                ("runs", ctypes.c_void_p), ("nports", ctypes.c_uint32),
+                ("pad1", ctypes.c_uint32), ("out", ctypes.c_void_p),
+                ("out_cap", ctypes.c_uint64), ("pk_off", ctypes.c_void_p),
+                ("pk_len", ctypes.c_void_p), ("ports", ctypes.c_void_p),
+                ("hdr", ctypes.c_void_p)]
+
+
 assert ctypes.sizeof(LdpPacket) == 24
 assert ctypes.sizeof(Dispatch) == 152
+assert ctypes.sizeof(Gather) == 136
 assert ctypes.sizeof(RxOpts) == 40
 
 # Every C function this module binds: name -> (restype, argtypes), as its
@@ -275,6 +290,11 @@ _SIGNATURES = {
     "pptk_tx_dispatch_device": (ci, (vp, P(Dispatch), vp, sz, vp)),
     "pptk_tx_dispatch_host": (ci, (P(Dispatch),)),
     "pptk_tx_dispatch_shape": (None, (P(u32), P(u32))),
+    # egress gather
+    "pptk_tx_gather_scratch_bytes": (sz, (u64, u32)),
+    "pptk_tx_gather_device": (ci, (vp, P(Gather), vp, sz, vp)),
+    "pptk_tx_gather_host": (ci, (P(Gather),)),
+    "pptk_tx_gather_shape": (None, (P(u32), P(u32))),
     # tuning
     "pptk_rx_set_tuning": (ci, (vp, ci, ci)),
     "pptk_rx_variant_count": (ci, ()),
@@ -922,6 +942,61 @@ class RxContext:
         return dict(hdr=hdr, ports=ports, list=out_list, out_off=out_off, out_len=out_len,
                     scratch=scratch)
 
+    def tx_gather_device(self, frames, n, max_entries, out_cap, nports=1, off=None, lens=None,
+                         stride=0, fixed_len=0, entries=None, d_entries=None, runs=None,
+                         out=None, pk_off=None, pk_len=None, ports=None, hdr=None, scratch=None,
+                         stream=None):
+        """pptk_tx_gather_device, asynchronous: the frames that the max_entries
+        entries of `entries` (int32 CUDA tensor, the list of tx_dispatch_device;
+        None: entry g is frame g) name, packed into one 256-byte aligned
+        region of `out` per port, every frame in a slot of whole 16-byte
+        chunks.  frames / off / lens / stride / fixed_len describe the n
+        source frames as for every batch op.  runs is the ports tensor of
+        tx_dispatch_device (None with nports 1: one region), d_entries a
+        device word that cuts max_entries (an int64 tensor, or an address
+        such as that of the dispatch header's `written`).  Allocates what is
+        not given -- out (uint8, out_cap bytes; none for out_cap 0), pk_off
+        (int64) and pk_len (int16) of max_entries entries (pass False for a
+        null pointer), ports (int64, 4 words per port:
+        records.GATHER_PORT_DTYPE), hdr (int64, records.GATHER_HDR_DTYPE) and
+        the scratch (uint8, tx_gather_scratch_bytes(max_entries, nports)) --
+        and returns dict(hdr, ports, out, pk_off, pk_len, scratch).  Download
+        ports, then each port's out[start, start + bytes)."""
+        dev = frames.device
+        if out_cap:
+            out = _empty(out, out_cap, "uint8", dev)
+        pk_off = None if pk_off is False else _empty(pk_off, max(max_entries, 1), "int64", dev)
+        pk_len = None if pk_len is False else _empty(pk_len, max(max_entries, 1), "int16", dev)
+        ports = _empty(ports, 4 * nports, "int64", dev)
+        hdr = _empty(hdr, 8, "int64", dev)
+        need = self._L.pptk_tx_gather_scratch_bytes(max_entries, nports)
+        scratch = _empty(scratch, max(need, 256), "uint8", dev)
+        g = Gather(frames=_ptr(frames), off=_ptr(off), len=_ptr(lens), stride=stride,
+                   fixed_len=fixed_len, n=n, list=_ptr(entries), max_entries=max_entries,
+                   d_entries=d_entries if isinstance(d_entries, int) else _ptr(d_entries),
+                   runs=_ptr(runs), nports=nports, out=_ptr(out) if out_cap else None,
+                   out_cap=out_cap, pk_off=_ptr(pk_off), pk_len=_ptr(pk_len), ports=_ptr(ports),
+                   hdr=_ptr(hdr))
+        _check(self._L.pptk_tx_gather_device(self._ctx, ctypes.byref(g), _dp(scratch),
+                                             scratch.numel() * scratch.element_size(),
+                                             _stream(stream, dev)), "pptk_tx_gather_device")
+        return dict(hdr=hdr, ports=ports, out=out, pk_off=pk_off, pk_len=pk_len, scratch=scratch)
+
+    @staticmethod
+    def tx_gather_host(*args, **kw):
+        """pptk_tx_gather_host (the module's tx_gather_host)."""
+        return tx_gather_host(*args, **kw)
+
+    @staticmethod
+    def tx_gather_scratch_bytes(max_entries, nports):
+        """pptk_tx_gather_scratch_bytes (the module's tx_gather_scratch_bytes)."""
+        return tx_gather_scratch_bytes(max_entries, nports)
+
+    @staticmethod
+    def tx_gather_shape():
+        """pptk_tx_gather_shape (the module's tx_gather_shape)."""
+        return tx_gather_shape()
+
     # ---- multi-GPU (RCCL) -------------------------------------------------
     def comm_create(self, nranks, rank, uid):
         """Join communicator `uid` (bytes from comm_uid()) as rank/nranks."""
@@ -1331,6 +1406,65 @@ def tx_dispatch_shape(lib_path=None):
     dispatch kernels."""
     b, w = ctypes.c_uint32(), ctypes.c_uint32()
     lib(lib_path).pptk_tx_dispatch_shape(ctypes.byref(b), ctypes.byref(w))
+    return b.value, w.value
+
+
+def tx_gather_host(frames, n, out_cap, nports=1, off=None, lens=None, stride=0, fixed_len=0,
+                   entries=None, max_entries=None, d_entries=None, runs=None, lib_path=None):
+    """pptk_tx_gather_host, the CPU statement of tx_gather_device, over NumPy
+    arrays: frames (uint8) with off (uint64) / lens (uint16) or stride /
+    fixed_len, n frames; entries (uint32) or None (entry g is frame g,
+    max_entries defaults to n); d_entries an int that cuts max_entries or
+    None; runs nports records.DISPATCH_PORT_DTYPE entries or None.  Returns
+    (hdr, ports, out, pk_off, pk_len): hdr one records.GATHER_HDR_DTYPE entry,
+    ports nports records.GATHER_PORT_DTYPE entries, out the out_cap bytes
+    (zero where the call wrote nothing), pk_off / pk_len cut to hdr.entries."""
+    from .records import DISPATCH_PORT_DTYPE, GATHER_HDR_DTYPE, GATHER_PORT_DTYPE
+
+    def arr(x, dtype):
+        return None if x is None else np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+
+    frames, off, lens = arr(frames, np.uint8), arr(off, np.uint64), arr(lens, np.uint16)
+    entries = arr(entries, np.uint32)
+    if any(x is not None and len(x) != n for x in (off, lens)):
+        raise ValueError("tx_gather_host: off and lens have n entries")
+    if max_entries is None:
+        max_entries = n if entries is None else len(entries)
+    if entries is not None and len(entries) < max_entries:
+        raise ValueError("tx_gather_host: entries has max_entries entries")
+    if runs is not None:
+        runs = np.ascontiguousarray(runs, dtype=DISPATCH_PORT_DTYPE).reshape(-1)
+        if len(runs) != nports:
+            raise ValueError("tx_gather_host: runs has nports entries")
+    out = np.zeros(max(out_cap, 1) + 255, np.uint8)
+    shift = -out.ctypes.data % 256
+    pk_off, pk_len = np.zeros(max(max_entries, 1), np.uint64), np.zeros(max(max_entries, 1), np.uint16)
+    ports, hdr = np.zeros(max(nports, 1), GATHER_PORT_DTYPE), np.zeros(1, GATHER_HDR_DTYPE)
+    word = None if d_entries is None else np.array([d_entries], np.uint64)
+
+    def p(x):
+        return None if x is None else x.ctypes.data
+
+    g = Gather(frames=p(frames), off=p(off), len=p(lens), stride=stride, fixed_len=fixed_len, n=n,
+               list=p(entries), max_entries=max_entries, d_entries=p(word), runs=p(runs),
+               nports=nports, out=out.ctypes.data + shift if out_cap else None, out_cap=out_cap,
+               pk_off=p(pk_off), pk_len=p(pk_len), ports=p(ports), hdr=p(hdr))
+    _check(lib(lib_path).pptk_tx_gather_host(ctypes.byref(g)), "pptk_tx_gather_host")
+    e = int(hdr["entries"][0])
+    return hdr[0], ports[:nports], out[shift:shift + out_cap], pk_off[:e], pk_len[:e]
+
+
+def tx_gather_scratch_bytes(max_entries, nports, lib_path=None):
+    """pptk_tx_gather_scratch_bytes: the device scratch a gather of up to
+    max_entries entries into nports regions needs (0 for max_entries = 0)."""
+    return lib(lib_path).pptk_tx_gather_scratch_bytes(max_entries, nports)
+
+
+def tx_gather_shape(lib_path=None):
+    """pptk_tx_gather_shape: (block_entries, scan_width) of the library's
+    gather kernels."""
+    b, w = ctypes.c_uint32(), ctypes.c_uint32()
+    lib(lib_path).pptk_tx_gather_shape(ctypes.byref(b), ctypes.byref(w))
     return b.value, w.value
 
 
